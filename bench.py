@@ -13,6 +13,14 @@ region is ONE call of the C-ABI entry point sabc_update() for K population updat
 
 For N > 1 the n_particles = 1e6 population is sharded over the ranks (strong scaling, the
 north-star target is quoted at n_particles = 1e6 on 8 GPUs); --particles-per-gpu switches to weak.
+
+A plain run does what its headline figure needs: set-up, the one-second pre-heat, the W warm-up
+updates, ONE timed region of exactly K updates (no kernel events in it), the result line.
+--full adds everything else: the median of 5 timed regions (--repeats), HIP events on the
+update kernel and the roofline built on them, the live VALU roofline, the CPU baseline and the
+posterior comparison with it, the figures read from profiles/, and for N > 1 the bracketed
+exchange updates and the one-shard check.  --dump-outputs DIR writes what the timed path
+computed (see dump_outputs) for output-for-output comparisons of two builds.
 """
 import argparse
 import json
@@ -27,11 +35,39 @@ import numpy as np  # noqa: E402
 
 SEED = 20241220
 HBM_PEAK_GBS = 8000.0          # MI355X HBM3E, /opt/skills/guides/MI355X_MICROARCH.md
+DUMP_LIMIT_BYTES = 64_000_000  # --dump-outputs: all files together
 
 
 def observed_mean():
     """y_obs: 100 draws of N(1.5, 1) with the fixed seed; only its mean is used."""
     return float(np.random.default_rng(SEED).normal(1.5, 1.0, 100).mean())
+
+
+def dump_outputs(path, h, theta, u, rho):
+    """--dump-outputs: what a caller of the timed path holds after its last update -- the particles (`population` n x d, `u` and
+    `rho` n x s, as in SABCresult), `eps`, the counters (n_simulation, n_accept, n_resampling, n_population_updates) and the
+    per-update history -- as float64 .npy files under `path`.  A population too large for DUMP_LIMIT_BYTES is written as a fixed,
+    seeded sample of particles, the same rows of every array, their indices in particle_index.npy.  A sharded run writes the
+    shard of the rank that calls this."""
+    eps_h, u_h, rho_h = h.history
+    c = h.counters
+    small = {"eps": h.eps, "eps_history": eps_h, "u_history": u_h, "rho_history": rho_h,
+             "counters": np.array([c["n_simulation"], c["n_accept"], c["n_resampling"], c["n_population_updates"]], dtype=np.float64)}
+    rows = {"population": theta.T, "u": u.T, "rho": rho.T}
+    n = theta.shape[1]
+    room = DUMP_LIMIT_BYTES - 4096 - sum(a.size * 8 for a in small.values())     # (4096: the .npy headers)
+    per_particle = 8 * sum(a.shape[1] for a in rows.values())
+    if n * per_particle > room:
+        m = max(room // (per_particle + 8), 0)          # (+ 8: the particle's index)
+        idx = np.sort(np.random.default_rng(SEED).choice(n, size=m, replace=False))
+        rows = {k: a[idx] for k, a in rows.items()}
+        small["particle_index"] = idx.astype(np.float64)
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(a, dtype=np.float64) for k, a in {**rows, **small}.items()}
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    return {"dir": path, "files": sorted(k + ".npy" for k in arrays), "bytes": sum(a.nbytes for a in arrays.values()),
+            "particles": len(rows["population"]), "of_particles": n, "sampled": "particle_index" in arrays}
 
 
 def cpu_baseline(n, updates, threads, warmup=0, steps=0, proposal="randomwalk", shard0=None):
@@ -259,8 +295,13 @@ def main():
     ap.add_argument("--n-obs", type=int, default=100, help="cfg2 only: draws per simulation (100 is the BASELINE workload)")
     ap.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"],
                     help="nccl (= RCCL) is the product path; gloo lets several ranks share one GPU to rehearse the N > 1 code path")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline figure (see the module docstring)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed in its last step to DIR/<name>.npy (float64, at most 64 MB)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--repeats", type=int, default=5, help="timed regions per process; `value` is their median")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="timed regions per process; `value` is their median (default: 1, with --full 5)")
     ap.add_argument("--preheat-seconds", type=float, default=1.0,
                     help="untimed launches of the bare generator loop (k_rng_peak) before the first timed region, until this much wall time has "
                          "passed (the GPU's clocks ramp over the first ~100 ms of load: five cold regions of 4 ms each measured 4.65 -> 5.46e9 in run order)")
@@ -277,6 +318,12 @@ def main():
                          "torch.distributed's RCCL on device pointers ('hooks-nccl': same wires, Python in the per-update path)")
     ap.add_argument("--launch-timeout", type=float, default=1500.0, help="--gpus N > 1 without a launcher: deadline for the ranks (s)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.dump_outputs and args.config == "host":
+        ap.error("--dump-outputs times the device path: not with --config host")
+    if args.repeats is None:
+        args.repeats = 5 if args.full else 1
 
     # `python bench.py --gpus N` without torch.distributed.run: start the N ranks ourselves -- BEFORE anything in this
     # process imports torch or touches HIP (a process that has initialised the GPU must not fork/exec workers)
@@ -335,11 +382,16 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    # The timed region is repeated R times in this process -- the population initialised again (sabc_initialize on the
-    # same handle: same seed, the very same trajectory as a fresh handle's), the same warm-up, the same K updates -- and
-    # `value` is the MEDIAN: one 4 ms sample says little (boxes and runs differ by a few per cent).  steps / warmup mean what
-    # they always meant.  The handle and its transport are set up ONCE: N ranks that map each other's memory (and an RCCL
-    # communicator each) are not torn down and rebuilt between the samples.
+    # With --repeats R > 1 (--full: 5) the timed region is repeated R times in this process -- the population initialised again
+    # (sabc_initialize on the same handle: same seed, the very same trajectory as a fresh handle's), the same warm-up, the same
+    # K updates -- and `value` is the MEDIAN: one 4 ms sample says little (boxes and runs differ by a few per cent).  steps /
+    # warmup mean what they always meant.  The handle and its transport are set up ONCE: N ranks that map each other's memory
+    # (and an RCCL communicator each) are not torn down and rebuilt between the samples.
+    # HIP events on the kernels feed the roofline and per-kernel figures only: a plain run leaves them out of its timed region.
+    if args.no_kernel_events or not (args.full or args.all_kernel_events or args.time_every_launch):
+        prof_level = 0
+    else:
+        prof_level = 2 if args.all_kernel_events else (3 if args.time_every_launch else 1)
     samples = []
     trace = os.environ.get("SABC_BENCH_TRACE")
 
@@ -388,7 +440,7 @@ def main():
         if W > 0:
             h.update(n_simulation=W * n, proposal=proposal)
         say(f"repeat {rep}: timed region")
-        h.profile_enable(0 if args.no_kernel_events else (2 if args.all_kernel_events else (3 if args.time_every_launch else 1)))
+        h.profile_enable(prof_level)
         barrier()
         syncs0, comm0, launches0, coll0 = h.host_syncs, h.comm_bytes, h.kernel_launches, h.collective_calls
         resampling0 = h.counters["n_resampling"]
@@ -413,14 +465,16 @@ def main():
     red_ms, red_n = med["red"]
     res_ms, res_n = med["res"]
     c = h.counters
-    th, _, _ = h.get_population(u=False, rho=False)
+    dump = bool(args.dump_outputs) and rank == 0
+    th, uu, rr = h.get_population(u=dump, rho=dump)
     state_after_timed = (dict(c), h.eps.copy())          # the last timed region's: the extra updates below move on
+    outputs = dump_outputs(args.dump_outputs, h, th, uu, rr) if dump else None
     # N > 1: what one update costs between the update kernels, measured on 10 MORE updates with every kernel bracketed
     # (level 2 adds ~4 us per bracket, so this is not part of the timed region): the reduce[-exchange]-control launch and,
     # on the collectives transport, the allreduce between k_reduce_partials and k_control
     exchange = None
     p2p_active_after_timed = bool(h.p2p_active) if world > 1 else False
-    if world > 1 and not args.no_kernel_events:
+    if args.full and world > 1 and not args.no_kernel_events:
         say("extra updates with every kernel bracketed")
         h.profile_enable(2)
         l0, c0 = h.kernel_launches, h.collective_calls
@@ -438,7 +492,7 @@ def main():
     # on over what install_collectives put underneath.  Otherwise the collectives never get a number on a node where the
     # peer-to-peer transport comes up.
     exchange_rccl = None
-    if world > 1 and transport == "p2p" and not args.no_kernel_events:
+    if args.full and world > 1 and transport == "p2p" and not args.no_kernel_events:
         say("leaving the peer-to-peer group: 10 bracketed updates over the collectives underneath")
         try:                                    # (a secondary measurement must not cost the run its line)
             h.p2p_disable()
@@ -453,7 +507,7 @@ def main():
         except Exception as e:
             exchange_rccl = {"transport": fallback, "error": repr(e)}
             r_n = None
-    if exchange_rccl is None and world > 1 and transport == "p2p" and not args.no_kernel_events:
+    if exchange_rccl is None and args.full and world > 1 and transport == "p2p" and not args.no_kernel_events:
         exchange_rccl = {"transport": fallback, "allreduce_us": (x_ms / x_n * 1e3) if x_n else None, "allreduces_timed": x_n,
                          "reduce_plus_control_us": r_ms / max(r_n, 1) * 1e3, "launches_per_update": (h.kernel_launches - l0) / 10.0,
                          "collective_calls_per_update": (h.collective_calls - c0) / 10.0, "us_per_update": t_x / 10.0 * 1e6,
@@ -464,7 +518,7 @@ def main():
     # N > 1: the same seed and calls on ONE shard of this rank's GPU.  The sharded run is shard-count independent by design
     # (Philox streams keyed by global particle id, rank-order sums): its accept count has to be this one's
     n1 = None
-    if world > 1 and rank == 0:
+    if args.full and world > 1 and rank == 0:
         say("n1_equivalent: the same calls on one shard")
         try:
             h1 = S.SabcHandle(n_particles=n, model=model, prior=prior, algorithm=alg, seed=SEED, device=device)
@@ -476,7 +530,7 @@ def main():
             e1 = h1.eps
         except Exception as e:
             n1, c1 = {"error": repr(e)}, None
-    if world > 1 and rank == 0 and n1 is None:
+    if args.full and world > 1 and rank == 0 and n1 is None:
         n1 = {"expected_equal": args.proposal == "randomwalk",
               "n_accept": c1["n_accept"], "n_resampling": c1["n_resampling"],
               "n_accept_equal": c1["n_accept"] == state_after_timed[0]["n_accept"],
@@ -503,7 +557,7 @@ def main():
         sims_per_launch = h.n_local if args.proposal == "randomwalk" else h.n_local / 2
         achieved = bytes_per_sim * sims_per_launch / avg_launch_s / 1e9 if launches else float("nan")
         valu = None
-        if launches and world == 1:
+        if args.full and launches and world == 1:
             peak = S.op_rng_peak(n_lanes=int(sims_per_launch), pairs_per_lane=max(normals_per_sim // 2, 1), repeats=10, device=device)
             in_kernel = normals_per_sim * sims_per_launch / avg_launch_s
             valu = {"bound": "valu", "achieved": in_kernel, "peak": peak, "unit": "normals/s", "frac": in_kernel / peak,
@@ -522,8 +576,8 @@ def main():
             "value_min": K * n / dts[-1], "value_max": K * n / dts[0], "repeats": len(samples),
             "preheat": dict(preheat, note="untimed launches of the bare generator loop before the first timed region (the device's clocks ramp over the first ~100 ms of load); --preheat-seconds 0 turns it off"),
             "values_in_run_order": [K * n / x["dt"] for x in samples],
-            "kernel_us_in_run_order": [(x["kern_ms"] / x["launches"] * 1e3) if x["launches"] else None for x in samples],
-            "value_note": "median of `repeats` timed regions in this process (population initialised again, same warm-up, same K updates each)",
+            "value_note": "median of `repeats` timed regions in this process (population initialised again, same warm-up, same K updates each)"
+                          if len(samples) > 1 else "one timed region of K updates after the warm-up",
             "unit": "particle-simulations/s",
             "n_gpus": world,
             "steps": K,
@@ -549,6 +603,28 @@ def main():
             # collectives underneath (0 = the whole run went peer to peer), and whether it is still on at the end
             "p2p_fallbacks": h.p2p_fallbacks if world > 1 else 0,
             "p2p_active_at_end": p2p_active_after_timed,
+            "normals_per_s": float(normals_per_sim) * K * n / dt,
+            # bytes landing in one shard's receive buffers per population update (allreduce of the fused sums; DE / Stretch:
+            # two allgathers of the inactive halves; on resamples the weight row and the rows the shard drew)
+            "comm_bytes_per_step": comm_bytes / K,
+            # kernels the library launched / collective calls it issued per population update in the timed region
+            # (resamples included), and -- N > 1 -- what the step between two update kernels costs
+            "launches_per_update": med["kernel_launches"] / K,
+            "persistent_launches": h.persistent_launches,      # > 0: small shard, the updates of a call in one launch
+            "persistent_lanes": h.persistent_lanes,            # ... with 16 | 4 | 1 lanes per particle (a team shares the generator's blocks)
+            "collective_calls_per_update": med["collective_calls"] / K,
+            "resamples_in_timed_region": c["n_resampling"] - resampling0,
+            "host_syncs_in_timed_region": syncs,
+            "init_s": t_init,
+            "state": {"n_accept": c["n_accept"], "n_resampling": c["n_resampling"],
+                      "n_population_updates": c["n_population_updates"], "eps": state_after_timed[1].tolist(),
+                      "shard0_mean": th.mean(1).tolist(), "shard0_var": th.var(1).tolist(), **analytic},
+        }
+        if outputs:
+            out["outputs"] = outputs
+        if args.full:
+            out.update({
+            "kernel_us_in_run_order": [(x["kern_ms"] / x["launches"] * 1e3) if x["launches"] else None for x in samples],
             "roofline": {
                 "bound": "hbm",
                 "achieved": achieved,
@@ -566,37 +642,27 @@ def main():
                         f"blocks + Box-Muller log/sqrt/sincos) per {bytes_per_sim} algorithmic bytes; the binding resource is VALU issue "
                         f"(valu_roofline: SQ counters show the VALU executing in ~95 % of the busy cycles); see normals_per_s",
             },
-            "normals_per_s": float(normals_per_sim) * K * n / dt,
             # the bound that actually binds: k_update's in-kernel normal rate against the bare Philox + Box-Muller
             # loop measured on this GPU right now (same lane count, same pairs per lane, nothing else in the loop)
             "valu_roofline": valu,
-            # bytes landing in one shard's receive buffers per population update (allreduce of the fused sums; DE / Stretch:
-            # two allgathers of the inactive halves; on resamples the weight row and the rows the shard drew)
-            "comm_bytes_per_step": comm_bytes / K,
-            # kernels the library launched / collective calls it issued per population update in the timed region
-            # (resamples included), and -- N > 1 -- what the step between two update kernels costs
-            "launches_per_update": med["kernel_launches"] / K,
-            "persistent_launches": h.persistent_launches,      # > 0: small shard, the updates of a call in one launch
-            "persistent_lanes": h.persistent_lanes,            # ... with 16 | 4 | 1 lanes per particle (a team shares the generator's blocks)
-            "collective_calls_per_update": med["collective_calls"] / K,
             "exchange": exchange,
             "exchange_rccl": exchange_rccl,
             "n1_equivalent": n1,
             "from_profiles": load_from_profiles(n, args.config) if world == 1 else {},
             "kernel_time_frac": (avg_launch_s * real_launches) / dt if launches else None,
             "reduce_us_per_step": red_ms / max(red_n, 1) * 1e3,
-            "resamples_in_timed_region": c["n_resampling"] - resampling0,
-            "host_syncs_in_timed_region": syncs,
-            "init_s": t_init,
-            "state": {"n_accept": c["n_accept"], "n_resampling": c["n_resampling"],
-                      "n_population_updates": c["n_population_updates"], "eps": state_after_timed[1].tolist(),
-                      "shard0_mean": th.mean(1).tolist(), "shard0_var": th.var(1).tolist(), **analytic},
-        }
+            })
         comparable = args.config == "cfg2" and args.algorithm == "single_eps" and args.n_obs == 100
-        if not args.no_cpu_baseline and world == 1 and args.config == "cfg2":
+        # The CPU leg runs --cpu-updates population updates (~0.16 s each at n = 1e6 on 16 threads); the posterior comparison
+        # needs the GPU's warm-up + K updates inside them and is left out, with a note, when they do not fit
+        cpu_skip = {"skipped": f"warm-up + steps = {W + K} population updates do not fit in --cpu-updates {args.cpu_updates}; "
+                               "raise --cpu-updates to compare"}
+        if args.full and not args.no_cpu_baseline and world == 1 and args.config == "cfg2":
             # the GPU box shows 256 logical CPUs but a one-GPU job's CPU share is 16: use that many threads
             threads = min(os.cpu_count() or 1, int(os.environ.get("SABC_CPU_THREADS", "16")))
-            out["cpu_baseline"], same = cpu_baseline(n, max(args.cpu_updates, W + K), threads, W, K, proposal=args.proposal)
+            out["cpu_baseline"], same = cpu_baseline(n, args.cpu_updates, threads, W, K, proposal=args.proposal)
+            if comparable and W + K > args.cpu_updates:
+                out["posterior_vs_cpu"] = cpu_skip
             if same and comparable:
                 gm, gv = float(th.mean()), float(th.var())
                 out["posterior_vs_cpu"] = {
@@ -604,7 +670,9 @@ def main():
                     "rel_err_mean": abs(gm / same["mean"] - 1.0), "rel_err_var": abs(gv / same["var"] - 1.0),
                     "n_accept_equal": same["n_accept"] == c["n_accept"], "updates": same["updates"],
                     "note": "same seed, same calls on the CPU restatement (oracle); the north star asks for moments within 1 %"}
-        elif not args.no_cpu_baseline and world > 1 and comparable:
+        elif args.full and not args.no_cpu_baseline and world > 1 and comparable and W + K > args.cpu_updates:
+            out["posterior_vs_cpu"] = cpu_skip
+        elif args.full and not args.no_cpu_baseline and world > 1 and comparable:
             # N > 1: the line validates itself.  The oracle runs the SAME initialize + warm-up + K updates (a bounded leg: W + K
             # updates, a few seconds on rank 0's CPU share while the other ranks wait) -- the accept and resample counts have
             # to be equal, epsilon and the moments of shard 0 (global particles 0 .. n_local - 1) those of the oracle's slice

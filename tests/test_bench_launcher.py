@@ -6,6 +6,7 @@ import subprocess
 import sys
 import time
 
+import numpy as np
 import psutil
 import pytest
 
@@ -86,12 +87,12 @@ def test_launcher_two_ranks_on_one_gpu(gpu):
 def test_launcher_two_ranks_peer_to_peer(gpu):
     """The same with the peer-to-peer transport on top of the gloo hooks (two processes mapping each other's memory with
     hipIpc): the line says so, counts no collective call in the timed region and one reduce-exchange-control launch per update
-    -- and VALIDATES ITSELF: the accept and resample counts equal the oracle's for the same seed and calls
+    -- and, with --full, VALIDATES ITSELF: the accept and resample counts equal the oracle's for the same seed and calls
     (`posterior_vs_cpu`, shard 0's moments against the oracle's same slice) and the one-shard run's on the same GPU
     (`n1_equivalent`); after the timed region every rank leaves the peer-to-peer group and the collectives underneath get
     their own numbers (`exchange_rccl`)."""
     r = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--dist-backend", "gloo", "--p2p", "on", "--steps", "6", "--warmup", "2",
-                        "--n-particles", "200000", "--repeats", "2"], env=_env(), stdout=subprocess.PIPE,
+                        "--n-particles", "200000", "--repeats", "2", "--full"], env=_env(), stdout=subprocess.PIPE,
                        stderr=subprocess.PIPE, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
@@ -111,3 +112,40 @@ def test_launcher_two_ranks_peer_to_peer(gpu):
     assert xr["transport"] == "hooks-gloo" and not xr["p2p_active"]
     assert xr["collective_calls_per_update"] >= 1.0 and xr["allreduces_timed"] >= 10 and xr["allreduce_us"] > 0
     assert xr["launches_per_update"] >= 3.0                   # k_update + k_reduce_partials + k_control (+ resamples)
+
+
+def test_steps_must_be_positive():
+    """--steps sets the number of timed updates: zero is refused before anything touches the GPU."""
+    r = subprocess.run([sys.executable, BENCH, "--steps", "0"], env=_env(), stdout=subprocess.PIPE, stderr=subprocess.PIPE,
+                       text=True, timeout=120)
+    assert r.returncode == 2 and "--steps must be at least 1" in r.stderr
+
+
+@pytest.mark.gpu
+def test_plain_run_times_the_steps_and_dumps_its_outputs(gpu, tmp_path):
+    """A plain run: one timed region of exactly --steps updates, none of the --full legs in its line; --dump-outputs writes
+    the timed path's arrays (float64, within 64 MB), and a second run with the same arguments writes the same arrays."""
+    lines, dumps = [], []
+    for k in range(2):
+        d = tmp_path / f"run{k}"
+        r = subprocess.run([sys.executable, BENCH, "--gpus", "1", "--steps", "3", "--warmup", "1", "--n-particles", "200000",
+                            "--preheat-seconds", "0", "--dump-outputs", str(d)], env=_env(), stdout=subprocess.PIPE,
+                           stderr=subprocess.PIPE, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines.append(json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1]))
+        dumps.append({f.name: np.load(f) for f in d.iterdir()})
+    out = lines[0]
+    assert out["steps"] == 3 and out["warmup"] == 1 and out["repeats"] == 1 and out["ms_per_step"] > 0
+    assert out["value"] == pytest.approx(3 * 200000 / (3 * out["ms_per_step"] * 1e-3))
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype"):
+        assert key in out
+    for key in ("cpu_baseline", "posterior_vs_cpu", "roofline", "valu_roofline", "from_profiles"):
+        assert key not in out
+    a, b = dumps
+    assert sorted(a) == sorted(out["outputs"]["files"]) and not out["outputs"]["sampled"]
+    assert sum(x.nbytes for x in a.values()) <= 64_000_000
+    assert a["population.npy"].shape == (200000, 1) and a["u.npy"].shape == a["rho.npy"].shape == (200000, 1)
+    assert a["counters.npy"].tolist()[1:] == [out["state"]["n_accept"], out["state"]["n_resampling"], 4]
+    for name, x in a.items():
+        assert x.dtype == np.float64, name
+        np.testing.assert_array_equal(x, b[name], err_msg=name)

@@ -15,7 +15,7 @@ cd /tmp
 for cfg in cfg2 cfg3 cfg4 cfg5; do
   steps=30; [ $cfg = cfg2 ] && steps=50
   rocprofv3 --kernel-trace --stats --output-format csv -d "$out/prof_${tag}_$cfg" -- \
-    python3 "$root/bench.py" --config $cfg --steps $steps --warmup 5 --no-cpu-baseline --repeats 1 \
+    python3 "$root/bench.py" --config $cfg --steps $steps --warmup 5 --no-cpu-baseline --repeats 1 --full \
     > "$out/prof_${tag}_$cfg.json" 2> "$out/prof_${tag}_$cfg.err"
   echo "profiled $cfg"
 done
