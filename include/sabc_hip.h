@@ -34,7 +34,7 @@ extern "C" {
 #define SABC_MAX_PARA 16        /* host-callback and source-compiled simulators: any d up to this (the reference takes any length(prior),      */
 #define SABC_MAX_STATS 64       /* SimulatedAnnealingABC.jl:163) and -- host-callback simulators -- any number of distances up to this (:164-167,181: */
                                 /* summaries of a time series easily number dozens)                                                            */
-#define SABC_MAX_SOURCE_STATS 16 /* a simulator compiled from source: its ECDF index lives in the fused kernel's LDS, s <= 16 */
+#define SABC_MAX_SOURCE_STATS 64 /* a simulator compiled from source: s <= 16 the fused kernel with its ECDF index in LDS, 16 < s <= 64 its wide form */
 #define SABC_MAX_JOINT_PARA 8   /* an MvNormal prior as data: d <= 8 (its Cholesky factor travels in kernel arguments)       */
 #define SABC_MAX_MODEL_PARAMS 32
 

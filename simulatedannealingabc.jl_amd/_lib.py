@@ -18,7 +18,7 @@ HEADER = os.path.normpath(os.path.join(_HERE, "..", "include", "sabc_hip.h"))
 ABI_VERSION = 6
 P2P_DESC_BYTES, P2P_MAX_WORLD = 512, 8
 MAX_PARA, MAX_STATS, MAX_MODEL_PARAMS = 16, 64, 32
-MAX_SOURCE_STATS = 16     # simulators compiled from source (SABC_MODEL_USER)
+MAX_SOURCE_STATS = 64     # simulators compiled from source (SABC_MODEL_USER)
 MAX_JOINT_PARA = 8
 MODEL_HOST, MODEL_GAUSS_IID, MODEL_GAUSS2D, MODEL_GK, MODEL_LV, MODEL_USER = 0, 1, 2, 3, 4, 5
 PRIOR_NORMAL, PRIOR_UNIFORM, PRIOR_EXPONENTIAL, PRIOR_LOGNORMAL, PRIOR_GAMMA, PRIOR_BETA, PRIOR_TRUNCNORMAL = 0, 1, 2, 3, 4, 5, 6

@@ -1660,6 +1660,10 @@ static int module_launch(hipFunction_t f, unsigned grid, unsigned block, hipStre
     }                                                                                             \
   } while (0)
 
+// workgroup of the per-particle kernels of a simulator from source (the wide form: kWideBlock, update_kernel.hpp)
+inline int source_block(const ModelDesc &m) { return source_wide(m.s) ? kWideBlock : kBlock; }
+inline unsigned source_blocks(const ModelDesc &m, int64_t n) { return (unsigned)((n + source_block(m) - 1) / source_block(m)); }
+
 inline unsigned gk_blocks(int64_t n) { return (unsigned)((n + kGkPerBlock - 1) / kGkPerBlock); }                       // k_simulate_gk
 inline unsigned gk_update_blocks(int64_t n) { return (unsigned)((n + kGkUpdatePerBlock - 1) / kGkUpdatePerBlock); }   // k_update_gk
 
@@ -1667,7 +1671,7 @@ int launch_prior_simulate(const ModelDesc &m, PopPtrs pp, hipStream_t stream, co
   if (pp.n_local <= 0) return 0;
   if (m.model_id == SABC_MODEL_USER) {
     if (!rtc || !rtc->prior_simulate) return (int)hipErrorInvalidValue;
-    return module_launch(rtc->prior_simulate, (unsigned)n_blocks(pp.n_local), kBlock, stream, nullptr, nullptr, m, pp);
+    return module_launch(rtc->prior_simulate, source_blocks(m, pp.n_local), source_block(m), stream, nullptr, nullptr, m, pp);
   }
   if (m.model_id == SABC_MODEL_GK) {
     hipLaunchKernelGGL(k_simulate_gk, dim3(gk_blocks(pp.n_local)), dim3(kBlock), 0, stream, m, (const double *)nullptr,
@@ -1690,6 +1694,7 @@ int launch_cdf_population(const ModelDesc &m, PopPtrs pp, CdfPtrs cdf, hipStream
 // workgroups (= partial rows) of one k_update launch over act_n particles
 int64_t update_rows(const ModelDesc &m, int64_t act_n) {
   if (act_n <= 0) return 0;
+  if (m.model_id == SABC_MODEL_USER && source_wide(m.s)) return source_blocks(m, act_n);   // k_update_wide
   return m.model_id == SABC_MODEL_GK ? (int64_t)gk_update_blocks(act_n)   // 4 waves x kGkParticlesPerWave particles per workgroup
                                      : (act_n + update_block_threads(m.s) - 1) / update_block_threads(m.s);   // one thread per particle
 }
@@ -1821,7 +1826,8 @@ int launch_update(const ModelDesc &m, const StepArgs &c, const ControlBlock *cb,
   double *out = partials + row0 * n_partials(m.d, m.s);
   if (m.model_id == SABC_MODEL_USER) {
     if (!rtc || c.prop_kind < 0 || c.prop_kind > 2 || !rtc->update[c.prop_kind]) return (int)hipErrorInvalidValue;
-    return module_launch(rtc->update[c.prop_kind], grid.x, update_block_threads(m.s), stream, ev0, ev1, m, c, cb, pp, cdf, pv, act_lo, act_n, out);
+    const unsigned b = source_wide(m.s) ? kWideBlock : update_block_threads(m.s);     // (k_update_wide | k_update)
+    return module_launch(rtc->update[c.prop_kind], grid.x, b, stream, ev0, ev1, m, c, cb, pp, cdf, pv, act_lo, act_n, out);
   }
   if (m.model_id == SABC_MODEL_GK) {
     const dim3 g((unsigned)update_rows(m, act_n));
@@ -2167,7 +2173,7 @@ int launch_simulate_batch(const ModelDesc &m, const double *theta, int64_t n, ui
   if (n <= 0) return 0;
   if (m.model_id == SABC_MODEL_USER) {
     if (!rtc || !rtc->simulate_batch) return (int)hipErrorInvalidValue;
-    return module_launch(rtc->simulate_batch, (unsigned)n_blocks(n), kBlock, stream, nullptr, nullptr, m, theta, n, pid0, iter,
+    return module_launch(rtc->simulate_batch, source_blocks(m, n), source_block(m), stream, nullptr, nullptr, m, theta, n, pid0, iter,
                          rho_out, gate);
   }
   if (m.model_id == SABC_MODEL_GK) {                  // (the gate is not looked at: the wave-cooperative simulator is a fixed

@@ -72,6 +72,13 @@ constexpr int update_block_threads(int s) { return s <= 1 ? SABC_UPDATE_BLOCK : 
 constexpr int update_min_waves(int s) {
   return s <= 1 ? SABC_UPDATE_MIN_WAVES : 3 * (cdf_coarse_entries(s) * s * 8 + 4096) <= 160 * 1024 ? SABC_UPDATE_MIN_WAVES_MS : SABC_UPDATE_MIN_WAVES;
 }
+// Simulators from source with more statistics than kNarrowStats (SABC_MAX_SOURCE_STATS = 64) take the WIDE form of the
+// per-particle kernels (update_kernel.hpp: k_update_wide, k_stats_wide, k_prior_simulate_wide, k_simulate_batch_wide; the distances
+// in LDS): the coarse ECDF index of 16 < s statistics does not fit the LDS, nor 1 + 2s + d + d(d+1)/2 sums the registers.
+// Workgroups of kWideBlock threads, one particle each, one partial row per workgroup.
+constexpr int kNarrowStats = 16;
+constexpr int kWideBlock = 64;
+constexpr bool source_wide(int s) { return s > kNarrowStats; }
 constexpr int kScanChunk = 1024;   // elements per scan block (4 per thread)
 // (a grid-stride variant of k_update with <= 1024 workgroups cost 20 more VGPRs and 11 % of its speed:
 // one workgroup per 256 (several statistics: 512) particles and dynamic workgroup scheduling stay)
@@ -106,7 +113,7 @@ struct PersistArgs {
 // does k_update_persistent<.., D, S, ..> fit the 160 KB of LDS of a CU?  (its static LDS: the ECDF coarse index, the generator
 // tables, the block reduction, a copy of the control block, the sums)  Shapes that do not keep the launch chain.
 constexpr bool persistent_fits(int d, int s) {
-  return (long)s * cdf_coarse_entries(s) * 8 + 3072 + (long)(update_block_threads(s) / 64 + 2) * n_partials(d, s) * 8 +
+  return !source_wide(s) && (long)s * cdf_coarse_entries(s) * 8 + 3072 + (long)(update_block_threads(s) / 64 + 2) * n_partials(d, s) * 8 +
          (long)update_block_threads(s) * 8 + (long)sizeof(ControlBlock) + (long)kMaxPartials * 8 + 2048 <= 156 * 1024;
 }
 

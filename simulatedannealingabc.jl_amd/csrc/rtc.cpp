@@ -204,10 +204,13 @@ int rtc_build(const char *user_source, int d, int s, const std::string &csrc_dir
 int rtc_compile(const char *user_source, int d, int s, const std::string &csrc_dir, RtcKernels *out, std::string *log,
                 size_t *code_size, bool user_prior, bool with_persistent) {
   constexpr int kMaxKernels = 16;
+  // more than kNarrowStats statistics: the wide kernels in the slots of the narrow ones, the launch chain only
+  const bool wide = source_wide(s);
+  if (wide) with_persistent = false;
   const int kKernels = with_persistent ? 16 : 7;
   HiprtcApi *api = hiprtc_api();
   if (!api) { *log = "libhiprtc.so could not be loaded: simulators from source need the hipRTC of ROCm"; return -1; }
-  if (d < 1 || d > SABC_MAX_PARA || s < 1 || s > SABC_MAX_SOURCE_STATS) { *log = "n_para / n_stats out of range (a simulator from source: d <= 16, s <= 16)"; return -1; }
+  if (d < 1 || d > SABC_MAX_PARA || s < 1 || s > SABC_MAX_SOURCE_STATS) { *log = "n_para / n_stats out of range (a simulator from source: d <= 16, s <= 64)"; return -1; }
   char tail[2048];
   std::snprintf(tail, sizeof(tail),
                 "\nnamespace sabc {\n"
@@ -225,10 +228,11 @@ int rtc_compile(const char *user_source, int d, int s, const std::string &csrc_d
   src += tail;
 
   char name[kMaxKernels][112];
-  std::snprintf(name[0], sizeof(name[0]), "sabc::k_prior_simulate<%d, %d, %d>", SABC_MODEL_USER, d, s);
-  for (int p = 0; p < 3; ++p) std::snprintf(name[1 + p], sizeof(name[1 + p]), "sabc::k_update<%d, %d, %d, %d>", SABC_MODEL_USER, d, s, p);
-  std::snprintf(name[4], sizeof(name[4]), "sabc::k_simulate_batch<%d, %d, %d>", SABC_MODEL_USER, d, s);
-  std::snprintf(name[5], sizeof(name[5]), "sabc::k_stats<%d, %d>", d, s);
+  const char *w = wide ? "_wide" : "";
+  std::snprintf(name[0], sizeof(name[0]), "sabc::k_prior_simulate%s<%d, %d, %d>", w, SABC_MODEL_USER, d, s);
+  for (int p = 0; p < 3; ++p) std::snprintf(name[1 + p], sizeof(name[1 + p]), "sabc::k_update%s<%d, %d, %d, %d>", w, SABC_MODEL_USER, d, s, p);
+  std::snprintf(name[4], sizeof(name[4]), "sabc::k_simulate_batch%s<%d, %d, %d>", w, SABC_MODEL_USER, d, s);
+  std::snprintf(name[5], sizeof(name[5]), "sabc::k_stats%s<%d, %d>", w, d, s);
   std::snprintf(name[6], sizeof(name[6]), "sabc::k_prior_op_t<%d>", d);
   for (int p = 0; p < 3; ++p) std::snprintf(name[7 + p], sizeof(name[7 + p]), "sabc::k_update_persistent<%d, %d, %d, %d>", SABC_MODEL_USER, d, s, p);
   for (int p = 0; p < 3; ++p) std::snprintf(name[10 + p], sizeof(name[10 + p]), "sabc::k_update_persistent<%d, %d, %d, %d, 4>", SABC_MODEL_USER, d, s, p);
@@ -331,6 +335,16 @@ int rtc_compile(const char *user_source, int d, int s, const std::string &csrc_d
   api->GetCodeSize(prog, &cs);
   if (code_size) *code_size = cs;
   if (!out) {                                         // compile-only check: every kernel must be there by name
+    // $SABC_RTC_CODE_OUT: the code object is also written to that file (its metadata -- registers, LDS, scratch -- can be
+    // read there without a device: tests/test_source_many_stats.py)
+    if (const char *dump = std::getenv("SABC_RTC_CODE_OUT")) {
+      std::vector<char> code(cs);
+      api->GetCode(prog, code.data());
+      FILE *fp = std::fopen(dump, "wb");
+      const bool ok = fp && std::fwrite(code.data(), 1, cs, fp) == cs;
+      if (fp) std::fclose(fp);
+      if (!ok) { *log = std::string("could not write the code object to ") + dump; api->DestroyProgram(&prog); return -1; }
+    }
     for (int i = 0; i < kKernels; ++i) {
       const char *lowered = nullptr;
       if (api->GetLoweredName(prog, name[i], &lowered) || !lowered) {

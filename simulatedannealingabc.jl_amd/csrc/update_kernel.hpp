@@ -391,4 +391,207 @@ k_simulate_batch(const ModelDesc m, const double *__restrict__ theta, const int6
   for (int j = 0; j < S; ++j) rho_out[(int64_t)j * n + i] = rho[j];
 }
 
+// ------------------------------------------------------------------------------------------
+// The wide form: simulators from source with 16 < S <= 64 statistics (kernels.hpp: kNarrowStats).  The narrow kernels keep the
+// coarse ECDF index of every statistic in LDS and a particle's distances, transforms and n_partials(D, S) sums in registers;
+// neither scales to 64 statistics (a 512 KB index, 281 sum columns).  Here:
+//  - a particle's distances live in a row of LDS: the simulator writes rho[j] through a pointer, at indices it computes at run
+//    time, which an array in registers would turn into scratch.  Rows of S | 1 doubles: an odd stride puts the j-th entries of
+//    the 64 lanes into distinct bank pairs;
+//  - the lookups take the three levels of cdf_apply_3level with the coarse level read from memory (8 KB per statistic, 384 KB
+//    at S = 48: it stays in the L2), the mid level and the knot line as the narrow form does: the same predicate on every level,
+//    the same ranks, the same u;
+//  - the partial row is reduced one column at a time (column_to_lds), in block_reduce_store's order.
+// Same streams (PURPOSE_PROP, PURPOSE_SIM, PURPOSE_ACCEPT), same row layout and place as k_update: the control step, the
+// collectives and the row exchange of the shards take the rows unchanged.
+// ------------------------------------------------------------------------------------------
+template <int S>
+constexpr int wide_row() { return S | 1; }
+
+// the narrow form's draft without its simulation: update_particle_draft<kDraftOnly, D, 1, ..> loads theta, proposes and gates
+// with the very code k_update runs; the wide kernel simulates into its LDS row
+constexpr int kDraftOnly = -1;
+template <int D, int S>
+struct Sim<kDraftOnly, D, S> {
+  static __device__ __forceinline__ void run(const ModelDesc &, const double *, uint64_t, uint64_t, double *, int = 0) {}
+};
+
+// f(StatIdx<0>()), .., f(StatIdx<N - 1>()): a loop whose index is a constant in every copy, however large the body (a register array
+// indexed in a `#pragma unroll` loop that the compiler declines to unroll -- 64 ECDF lookups -- would be left in scratch)
+template <int J>
+struct StatIdx { static constexpr int value = J; };
+template <int J, int N, class F>
+__device__ __forceinline__ void static_for(F &f) {
+  if constexpr (J < N) {
+    f(StatIdx<J>());
+    static_for<J + 1, N>(f);
+  }
+}
+
+// one column of a workgroup's partial row: the wave's sum by shuffles, into sm[wave][c]
+__device__ __forceinline__ void column_to_lds(double v, const int c, double *sm, const int np) {
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) v += __shfl_down(v, off, 64);
+  if ((threadIdx.x & 63) == 0) sm[(threadIdx.x >> 6) * np + c] = v;
+}
+
+// ... and the sum over the waves, in wave order, into the row
+template <int NW>
+__device__ __forceinline__ void columns_store(const double *sm, const int np, double *__restrict__ out) {
+  __syncthreads();
+  for (int c = threadIdx.x; c < np; c += NW * 64) {
+    double a = sm[c];
+#pragma unroll
+    for (int w = 1; w < NW; ++w) a += sm[w * np + c];
+    out[c] = a;
+  }
+}
+
+// the theta columns of moment_terms: theta - pivot and the lower triangle of its outer product, from column c0 on
+template <int D>
+__device__ __forceinline__ void theta_columns(const double *__restrict__ pivot, const double (&th)[D], const bool live, const int c0,
+                                              double *sm, const int np) {
+  double dk[D];
+#pragma unroll
+  for (int k = 0; k < D; ++k) dk[k] = live ? th[k] - pivot[k] : 0.0;
+#pragma unroll
+  for (int k = 0; k < D; ++k) column_to_lds(dk[k], c0 + k, sm, np);
+  int q = c0 + D;
+#pragma unroll
+  for (int k = 0; k < D; ++k)
+#pragma unroll
+    for (int l = 0; l <= k; ++l) column_to_lds(dk[k] * dk[l], q++, sm, np);
+}
+
+// K4, wide: propose -> prior gate -> simulate -> ECDF -> annealed MH accept -> store -> partial row (:308-331)
+template <int MODEL, int D, int S, int PROP>
+__global__ void __launch_bounds__(kWideBlock)
+k_update_wide(const ModelDesc m, const StepArgs c, const ControlBlock *__restrict__ cb, const PopPtrs pp, const CdfPtrs cdf,
+              const PartnerView pv, const int64_t act_lo, const int64_t act_n, double *__restrict__ partials) {
+  constexpr int NP = n_partials(D, S), NW = kWideBlock / 64, R = wide_row<S>(), kCoarse = cdf_coarse_entries(S);
+  if (cb->halt) return;                    // queued ahead of a resample decision that fired (uniform)
+  rng_tables_load();
+  __shared__ double rows[kWideBlock * R];  // the particles' distances: rho_p, after the decision rho_p - rho (accepted) or 0
+  __shared__ double sm[NW * NP];
+  __syncthreads();                         // publishes the generator tables
+  double *rho = rows + threadIdx.x * R;
+  const int64_t t = (int64_t)blockIdx.x * kWideBlock + threadIdx.x;
+  const bool live = t < act_n;
+  const int64_t li = act_lo + t;
+  double th[D];
+  bool accepted = false;
+  if (live) {
+    const uint64_t gid = (uint64_t)(pp.gid0 + li);
+    double thp[D], lpp, logf;
+    {
+      ParticleDraft<D, 1> q;               // (q.u, q.rp: unused)
+      update_particle_draft<kDraftOnly, D, 1, PROP, false, 1>(m, c.iter, c.prop_p0, c.prop_p1, cb, pp, pv, li, gid, q);   // :311-314
+#pragma unroll
+      for (int k = 0; k < D; ++k) { th[k] = q.th[k]; thp[k] = q.thp[k]; }
+      lpp = q.lpp;
+      logf = q.logf;
+    }
+    for (int j = 0; j < S; ++j) rho[j] = 0.0;
+    if (lpp > -INFINITY) Sim<MODEL, D, S>::run(m, thp, gid, c.iter, rho);                              // :315
+    // the statistics one at a time, ascending j: u_p (registers) and sum_j (u_j - u_p,j) / eps_j as k_update sums it
+    double up[S];
+    double log_accept = -INFINITY;
+    auto zero = [&](auto jj) { up[decltype(jj)::value] = 0.0; };
+    static_for<0, S>(zero);
+    if (lpp > -INFINITY) {
+      double a = 0.0;
+      auto lookup = [&](auto jj) {
+        constexpr int j = decltype(jj)::value;
+        up[j] = cdf_apply_3level<kCoarse>(cdf.knots + (int64_t)j * cdf.stride, cdf.len[j], cdf.shift[j], cdf.coarse + (int64_t)j * kCoarse,
+                                          cdf.mid + (int64_t)j * cdf.mid_stride, rho[j]);                  // :316
+        const double e = (cb->eps_len == 1) ? cb->eps[0] : cb->eps[j];
+        a += (pp.pop[(int64_t)(D + j) * pp.cap + li] - up[j]) / e;                                      // :319
+      };
+      static_for<0, S>(lookup);
+      log_accept = lpp - prior_logpdf<D>(m, th) + a + logf;                                           // :318-319
+    }
+    const u32x4 wa = stream_block(m.seed, gid, PURPOSE_ACCEPT, c.iter, 0);
+    accepted = -0.5 * neg2_log_tab(u52(wa.x, wa.y)) < log_accept;                                       // :324
+    if (accepted) {                                                                                     // :325-329
+#pragma unroll
+      for (int k = 0; k < D; ++k) {
+        th[k] = thp[k];
+        pp.pop[(int64_t)k * pp.cap + li] = thp[k];
+      }
+      auto store = [&](auto jj) {
+        constexpr int j = decltype(jj)::value;
+        const double r = rho[j];
+        rho[j] = r - pp.rho[(int64_t)j * pp.cap + li];
+        pp.pop[(int64_t)(D + j) * pp.cap + li] = up[j];
+        pp.rho[(int64_t)j * pp.cap + li] = r;
+      };
+      static_for<0, S>(store);
+    } else {
+      for (int j = 0; j < S; ++j) rho[j] = 0.0;
+    }
+  }
+  // the partial row: accepted, u as it stands, the change of rho, theta - pivot and its products (moment_terms)
+  column_to_lds(accepted ? 1.0 : 0.0, 0, sm, NP);
+  for (int j = 0; j < S; ++j) column_to_lds(live ? pp.pop[(int64_t)(D + j) * pp.cap + li] : 0.0, 1 + j, sm, NP);
+  for (int j = 0; j < S; ++j) column_to_lds(live ? rho[j] : 0.0, 1 + S + j, sm, NP);
+  theta_columns<D>(cb->pivot, th, live, 1 + 2 * S, sm, NP);
+  columns_store<NW>(sm, NP, partials + (int64_t)blockIdx.x * NP);
+}
+
+// moment sums of the shard as it stands (k_stats), wide: one column at a time
+template <int D, int S>
+__global__ void __launch_bounds__(kBlock)
+k_stats_wide(const ControlBlock *__restrict__ cb, const PopPtrs pp, double *__restrict__ partials) {
+  constexpr int NP = n_partials(D, S), NW = kBlock / 64;
+  __shared__ double sm[NW * NP];
+  const int64_t li = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  const bool live = li < pp.n_local;
+  double th[D];
+#pragma unroll
+  for (int k = 0; k < D; ++k) th[k] = live ? pp.pop[(int64_t)k * pp.cap + li] : 0.0;
+  column_to_lds(0.0, 0, sm, NP);
+  for (int j = 0; j < S; ++j) column_to_lds(live ? pp.pop[(int64_t)(D + j) * pp.cap + li] : 0.0, 1 + j, sm, NP);
+  for (int j = 0; j < S; ++j) column_to_lds(live ? pp.rho[(int64_t)j * pp.cap + li] : 0.0, 1 + S + j, sm, NP);
+  theta_columns<D>(cb->pivot, th, live, 1 + 2 * S, sm, NP);
+  columns_store<NW>(sm, NP, partials + (int64_t)blockIdx.x * NP);
+}
+
+// K1, wide (:172-179): the distances through a row of LDS; workgroups of kWideBlock
+template <int MODEL, int D, int S>
+__global__ void __launch_bounds__(kWideBlock) k_prior_simulate_wide(const ModelDesc m, const PopPtrs pp) {
+  rng_tables_init();
+  __shared__ double rows[kWideBlock * wide_row<S>()];
+  const int64_t li = (int64_t)blockIdx.x * kWideBlock + threadIdx.x;
+  if (li >= pp.n_local) return;
+  const uint64_t gid = (uint64_t)(pp.gid0 + li);
+  double *rho = rows + threadIdx.x * wide_row<S>();
+  double th[D];
+  prior_sample<D>(m, gid, th);
+  for (int j = 0; j < S; ++j) rho[j] = 0.0;
+  Sim<MODEL, D, S>::run(m, th, gid, 0, rho);
+#pragma unroll
+  for (int k = 0; k < D; ++k) pp.pop[(int64_t)k * pp.cap + li] = th[k];
+  for (int j = 0; j < S; ++j) pp.rho[(int64_t)j * pp.cap + li] = rho[j];
+}
+
+// k_simulate_batch, wide
+template <int MODEL, int D, int S>
+__global__ void __launch_bounds__(kWideBlock)
+k_simulate_batch_wide(const ModelDesc m, const double *__restrict__ theta, const int64_t n, const uint64_t pid0,
+                      const uint64_t iter, double *__restrict__ rho_out, const unsigned char *__restrict__ gate) {
+  rng_tables_init();
+  __shared__ double rows[kWideBlock * wide_row<S>()];
+  const int64_t i = (int64_t)blockIdx.x * kWideBlock + threadIdx.x;
+  if (i >= n) return;
+  double *rho = rows + threadIdx.x * wide_row<S>();
+  for (int j = 0; j < S; ++j) rho[j] = 0.0;
+  if (!gate || gate[i]) {
+    double th[D];
+#pragma unroll
+    for (int k = 0; k < D; ++k) th[k] = theta[(int64_t)k * n + i];
+    Sim<MODEL, D, S>::run(m, th, pid0 + (uint64_t)i, iter, rho);
+  }
+  for (int j = 0; j < S; ++j) rho_out[(int64_t)j * n + i] = rho[j];
+}
+
 }  // namespace sabc

@@ -138,7 +138,8 @@ end
 model_id(::HostDistance) = Int32(0)
 
 # ---- f_dist as HIP source, compiled at run time into the fused update kernel (include/sabc_hip.h:
-#      sabc_register_device_simulator); with a SourcePrior the same source also defines the prior (prior_joint = 3) ----
+#      sabc_register_device_simulator); with a SourcePrior the same source also defines the prior (prior_joint = 3).
+#      n_stats <= 64; observations belong in the source (a __constant__ array), params holds at most 32 values ----
 struct DeviceSource <: DeviceDistance
     source::String
     n_para::Int

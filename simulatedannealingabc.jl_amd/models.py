@@ -143,7 +143,9 @@ class DeviceSource(DeviceDistance):
     order -- the loop to draw the bulk of a simulation with: small populations (one launch per call, a team of 4 or 16
     lanes per particle) then generate 16 or 64 pairs at a time, four blocks per lane.  The simulator must be a function of its arguments and
     its draws alone (the lanes of a quad run it side by side).  `params` is the `params` list given here.  The source is compiled at run time (hipRTC, gfx950) into
-    the same fused propose -> simulate -> ECDF -> accept kernel as the built-in simulators."""
+    the same fused propose -> simulate -> ECDF -> accept kernel as the built-in simulators.  n_stats <= 64 (_lib.MAX_SOURCE_STATS;
+    above 16 the wide form of the kernels).  `params` holds at most 32 values: observations the simulator compares
+    against (a time series) belong in the source itself, e.g. `__constant__ double kObs[48] = {...};`."""
     model_id = _lib.MODEL_USER
 
     def __init__(self, hip_source: str, n_para: int, n_stats: int, params=()):
