@@ -5,6 +5,7 @@
 #include <unistd.h>
 #include <atomic>
 #include <chrono>
+#include <cmath>
 #include <string>
 #include <cstdio>
 #include <cstdlib>
@@ -214,7 +215,9 @@ int HipBackend::allocate(const ModelDesc &m, const Shard &sh) {
   HB_CHECK(pop_alloc(&rho_, (size_t)m.s * cap * sizeof(double)), "hipMalloc(rho)");
   HB_CHECK(hipMemsetAsync(rho_, 0, (size_t)m.s * cap * sizeof(double), stream_), "hipMemset(rho)");
   HB_CHECK(hipMalloc((void **)&coarse_, (size_t)m.s * cdf_coarse_entries(m.s) * sizeof(double)), "hipMalloc(coarse)");
-  knot_stride_ = (((int64_t)N + 2 + 15) / 16) * 16;       // every table starts on a 128-byte line
+  // every table starts on a 128-byte line, and a whole line of +inf stays behind the longest one (N + 2 knots): the searches
+  // read up to 15 knots past a table's last knot, which must never be the next statistic's first knots or past the allocation
+  knot_stride_ = (((int64_t)N + 2 + 15) / 16) * 16 + 16;
   HB_CHECK(hipMalloc((void **)&knots_, (size_t)m.s * (size_t)knot_stride_ * sizeof(double)), "hipMalloc(knots)");
   mid_stride_ = cdf_mid_stride(knot_stride_);
   HB_CHECK(hipMalloc((void **)&mid_, (size_t)m.s * (size_t)mid_stride_ * sizeof(double)), "hipMalloc(mid)");
@@ -976,7 +979,13 @@ int HipBackend::get_knots(int stat, double *out, int64_t len) {
 }
 
 int HipBackend::set_knots(int stat, const double *knots, int64_t len) {
-  if (stat < 0 || stat >= m_.s || len < 3 || len > knot_stride_) { err_ = "set_knots: bad statistic index or length"; return -1; }
+  if (stat < 0 || stat >= m_.s || len < 3 || len > knot_stride_ - 16) { err_ = "set_knots: bad statistic index or length"; return -1; }
+  // every lookup assumes a sorted table of finite non-negative distances (a NaN breaks the search's predicate, +inf is the
+  // padding behind the table): refuse anything else before the handle's table is touched
+  for (int64_t i = 0; i < len; ++i) {
+    if (!(std::isfinite(knots[i]) && knots[i] >= 0.0)) { err_ = "set_knots: knots must be finite and non-negative"; return -1; }
+    if (i > 0 && knots[i] < knots[i - 1]) { err_ = "set_knots: knots must be non-decreasing"; return -1; }
+  }
   HB_CHECK(hipMemcpyAsync(knots_ + (int64_t)stat * knot_stride_, knots, (size_t)len * sizeof(double), hipMemcpyHostToDevice, stream_), "memcpy(knots)");
   HB_CHECK(hipStreamSynchronize(stream_), "hipStreamSynchronize");
   cdf_len_[stat] = len;
