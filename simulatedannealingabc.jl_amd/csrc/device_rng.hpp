@@ -65,7 +65,8 @@ __device__ __forceinline__ u32x4 stream_block(uint64_t seed, uint64_t pid, uint3
 
 // (x + 1/2) * 2^-52 with x = (low 20 bits of hi):(all of lo): exact in binary64, in (0,1).
 // Built without a shift or an int->fp conversion: those 52 bits ARE the mantissa of a double in [1,2)
-// (one v_and_or on the high word), and (1 - 2^-53) is subtracted, which is exact.
+// (a v_and_b32 and a v_or_b32 on the high word: a gfx9 VOP3 instruction takes ONE literal, and 0xFFFFF and 0x3FF00000 are
+// two; loop::u52 below, with the exponent word in a register, is the one v_and_or_b32), and (1 - 2^-53) is subtracted, which is exact.
 __device__ __forceinline__ double u52(uint32_t hi, uint32_t lo) {
   const double d = __hiloint2double((int)(0x3FF00000u | (hi & 0xFFFFFu)), (int)lo);
   return d - 0x1.fffffffffffffp-1;
@@ -256,6 +257,118 @@ __device__ __forceinline__ void box_muller(const u32x4 w, double &z0, double &z1
   z1 = r * sn;
 }
 
+// ---- the same generator, re-spelled for the simulators' loop (NormalStream::for_pairs with a lane per particle) --------------
+// The update kernels sit at the VALU issue ceiling and nine tenths of their instructions come from that loop, so it is worth
+// spelling it for the instruction count: 94 -> 85 VALU instructions per pair (tests/test_generator_isa.py).  Nothing here
+// changes arithmetic -- same words, same products, same FMAs in the same order (tests/test_generator_bits.py holds the bits
+// against the build before) --, and the functions above stay as they are for every other draw: a re-spelled one-off draw gains
+// nothing and shifts the register allocation of kernels that sit on their register cap.
+namespace loop {
+
+// Philox with the wave-uniform half of rounds 1-2 on the scalar unit.  In the streams' layout (stream_block) c1, c2, c3 and the
+// key are the same on every lane of a wave, only c0 = the particle id differs: round 1's M1 c2 and n0 and round 2's M0 c0 are
+// uniform.  xor3's builtin is a VALU instruction whatever its operands are and pins them (and the two multiplies behind) to
+// the VALU; the plain XOR leaves them to the scalar unit (s_xor_b32, s_mul_i32, s_mul_hi_u32), idle in this loop.  Rounds 3-10
+// keep the three-input XOR (the compiler does not form it by itself).
+__device__ __forceinline__ u32x4 philox4x32_10(uint32_t k0, uint32_t k1, uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3) {
+#pragma unroll
+  for (int r = 0; r < 10; ++r) {
+    const uint64_t p0 = (uint64_t)0xD2511F53u * c0;
+    const uint64_t p1 = (uint64_t)0xCD9E8D57u * c2;
+    const uint32_t n0 = r < 2 ? (uint32_t)(p1 >> 32) ^ c1 ^ k0 : xor3((uint32_t)(p1 >> 32), c1, k0);
+    const uint32_t n2 = r < 2 ? (uint32_t)(p0 >> 32) ^ c3 ^ k1 : xor3((uint32_t)(p0 >> 32), c3, k1);
+    c1 = (uint32_t)p1;
+    c3 = (uint32_t)p0;
+    c0 = n0;
+    c2 = n2;
+    k0 += 0x9E3779B9u;
+    k1 += 0xBB67AE85u;
+  }
+  return u32x4{c0, c1, c2, c3};
+}
+
+__device__ __forceinline__ u32x4 stream_block(uint64_t seed, uint64_t pid, uint32_t purpose, uint64_t iter, uint32_t k) {
+  const uint32_t c3 = (purpose & 0xFFu) | ((uint32_t)(pid >> 32) << 8) | ((uint32_t)((iter >> 32) & 0xFFu) << 24);
+  return loop::philox4x32_10((uint32_t)seed, (uint32_t)(seed >> 32), (uint32_t)pid, k, (uint32_t)iter, c3);
+}
+
+// The constants of a pair that the instruction set cannot take as immediates where they are used, held in registers that the
+// compiler has to treat as unknown values, so that it cannot rebuild them in front of every use (v_mov_b32: four per pair).
+// Loaded ONCE in front of the loop.
+struct Regs {
+  uint32_t one_hi;     // 0x3FF00000, the high word of 1.0, in a vector register: u52 is one v_and_or_b32
+  double big;          // 0x1.8p52, sincos_2pi_tab's add-a-big-number constant, in a vector register pair ...
+  double k32;          // ... and 32.0 in a scalar pair: fma(u, 32, big) is the three-address v_fma_f64 that reads big where it
+                       // is (with 32.0 as a literal it is the two-address v_fmac_f64 on a copy of big)
+  __device__ __forceinline__ static Regs load() {
+    Regs r{0x3FF00000u, 0x1.8p52, 32.0};
+    asm("" : "+v"(r.one_hi));
+    asm("" : "+v"(r.big));
+    asm("" : "+s"(r.k32));
+    return r;
+  }
+};
+
+__device__ __forceinline__ double u52(uint32_t hi, uint32_t lo, const Regs &c) {
+  const double d = __hiloint2double((int)(c.one_hi | (hi & 0xFFFFFu)), (int)lo);
+  return d - 0x1.fffffffffffffp-1;
+}
+
+// neg2_log_tab with the power of two in the TABLE ENTRY's exponent, not in x's: s = m (-2 inv) + 2 with m = x 2^-E is also
+// x (2^-E (-2 inv)) + 2.  Both scalings are exact and the two products are the same real number, so the fma rounds to the same
+// s; but a new high word on x costs a copy of its low word (the pair x lives in is still read), on the loaded entry it does not.
+// (x in [2^-1000, 2^1000]: the entry's exponent must stay in range.  Box-Muller's x is in (0, 1).)
+__device__ __forceinline__ double neg2_log_tab(double x) {
+  const uint32_t hi = (uint32_t)__double2hiint(x);
+  const uint32_t t = hi + 0x800u;
+  const uint32_t tp = t + (75u << 13);
+  const int nE = 1023 - (int)(tp >> 20);
+  const double2 e = rng_tables().logt[(t >> 13) & 127u];
+  const double ex = __hiloint2double((int)((uint32_t)__double2hiint(e.x) + ((uint32_t)nE << 20)), __double2loint(e.x));
+  const double s = fma(x, ex, 2.0);
+  double p = 1.0 / 448.0;
+  p = fma(p, s, 1.0 / 192.0);
+  p = fma(p, s, 1.0 / 80.0);
+  p = fma(p, s, 1.0 / 32.0);
+  p = fma(p, s, 1.0 / 12.0);
+  p = fma(p, s, 0.25);
+  const double l = fma(s * s, p, s);
+  const double nEd = (double)nE;
+  return fma(nEd, 2.0 * 6.93147180559945309417e-01, e.y) + l;
+}
+
+__device__ __forceinline__ void sincos_2pi_tab(double u, double &sn, double &cs, const Regs &c) {
+  const double tm = fma(u, c.k32, c.big);
+  const double kf = tm - c.big;
+  const double r = 1.96349540849362077404e-01 * fma(u, 32.0, -kf);
+  const double2 sc = rng_tables().sct[__double2loint(tm)];
+  const double r2 = r * r;
+  double p = 1.0 / 362880.0;
+  p = fma(p, r2, -1.0 / 5040.0);
+  p = fma(p, r2, 1.0 / 120.0);
+  p = fma(p, r2, -1.0 / 6.0);
+  const double sr = fma(r * r2, p, r);
+  double q = 1.0 / 40320.0;
+  q = fma(q, r2, -1.0 / 720.0);
+  q = fma(q, r2, 1.0 / 24.0);
+  q = fma(q, r2, -0.5);
+  q *= r2;
+  sn = sc.x + fma(sc.x, q, sc.y * sr);
+  cs = sc.y + fma(sc.y, q, -(sc.x * sr));
+}
+
+__device__ __forceinline__ void box_muller(const u32x4 w, double &z0, double &z1, const Regs &c) {
+  const double ua = loop::u52(w.x, w.y, c);
+  const double ub = loop::u52(w.z, w.w, c);
+  const double r = sqrt_fast(loop::neg2_log_tab(ua));
+  double sn, cs;
+  loop::sincos_2pi_tab(ub, sn, cs, c);
+  z0 = r * cs;
+  z1 = r * sn;
+}
+
+}  // namespace loop
+
 // A TEAM of W = 4 or 16 lanes (a quad | a row of the wave) that run one particle side by side: the value lane (team base + J)
 // holds, on every lane of the team -- one DPP move per 32-bit half, no LDS (quad_perm [J, J, J, J] | row_newbcast:J).
 template <int W, int J>
@@ -282,6 +395,10 @@ __device__ __forceinline__ double team_pick(const double v, const uint32_t j) {
 #define SABC_SIM_UNROLL 2
 #endif
 
+// NormalStream's coop for a lane per particle whose for_pairs stays the plain loop over pair(): the re-spelled loop holds three
+// more vector and two more scalar registers; kernels that sit on their register cap (kernels.hpp: update_loop_coop) keep this one
+constexpr int kCoopPlainLoop = -1;
+
 template <int... J> struct lane_seq {};
 template <int N, int... J> struct make_lane_seq : make_lane_seq<N - 1, N - 1, J...> {};
 template <int... J> struct make_lane_seq<0, J...> { using type = lane_seq<J...>; };
@@ -297,7 +414,8 @@ template <int... J> struct make_lane_seq<0, J...> { using type = lane_seq<J...>;
 // make the same requests -- they do: their control flow depends on the particle's data only.
 //
 // for_pairs(n, f) -- f(z0, z1) for the next n pairs of the stream, in stream order -- is the loop a simulator should draw its
-// bulk with.  A lane per particle: the plain loop over pair(), two trips unrolled.  A team per particle: 4 W pairs at a time,
+// bulk with.  A lane per particle: the loop over the stream's blocks, two trips unrolled, in its
+// re-spelled form (namespace loop above; kCoopPlainLoop: the plain loop over pair()).  A team per particle: 4 W pairs at a time,
 // FOUR blocks per lane side by side (a single block per lane is a chain of ~100 dependent instructions: with one wave on the
 // SIMD its latency, not its issue, is what the team would wait for), handed out through DPP broadcasts whose lane is a
 // compile-time constant; the rest -- fewer than 4 W pairs -- in one more group of as many blocks per lane as it takes.  pair() / uniform_pair() / next() keep working in either mode, one
@@ -308,6 +426,7 @@ struct NormalStream {
   double spare;
   bool have;
   int coop;                      // 0: every lane its own stream | 4, 16: the lanes of a team share one (see above)
+                                 // | kCoopPlainLoop: as 0, with for_pairs as the plain loop over pair()
   int buf_block;                 // coop: first block of the group of W this lane holds one block of (-1: none) ...
   bool buf_uniform;              // ... as uniforms (uniform_pair) or as a Box-Muller pair
   double b0, b1;
@@ -329,14 +448,8 @@ struct NormalStream {
   }
   template <class F>
   __device__ __forceinline__ void for_pairs(const int n, F &&f) {
-    if (coop == 4) { for_pairs_team<4>(n, f); return; }
-    if (coop == 16) { for_pairs_team<16>(n, f); return; }
-#pragma unroll SABC_SIM_UNROLL
-    for (int i = 0; i < n; ++i) {
-      double z0, z1;
-      pair(z0, z1);
-      f(z0, z1);
-    }
+    if (coop == 0) { for_pairs_lane(n, f); return; }
+    for_pairs_plain(n, f);
   }
   __device__ __forceinline__ double next() {
     if (have) { have = false; return spare; }
@@ -347,6 +460,29 @@ struct NormalStream {
   }
 
  private:
+  // a lane per particle, the re-spelled loop (namespace loop)
+  template <class F>
+  __device__ __forceinline__ void for_pairs_lane(const int n, F &f) {
+    const loop::Regs c = loop::Regs::load();           // once per loop, not per pair
+#pragma unroll SABC_SIM_UNROLL
+    for (int i = 0; i < n; ++i) {
+      double z0, z1;
+      loop::box_muller(loop::stream_block(seed, pid, purpose, iter, k++), z0, z1, c);
+      f(z0, z1);
+    }
+  }
+  // a team per particle, or a lane per particle with the plain loop over pair() (kCoopPlainLoop)
+  template <class F>
+  __device__ __forceinline__ void for_pairs_plain(const int n, F &&f) {
+    if (coop == 4) { for_pairs_team<4>(n, f); return; }
+    if (coop == 16) { for_pairs_team<16>(n, f); return; }
+#pragma unroll SABC_SIM_UNROLL
+    for (int i = 0; i < n; ++i) {
+      double z0, z1;
+      pair(z0, z1);
+      f(z0, z1);
+    }
+  }
   template <int W, class F, int... J>
   __device__ __forceinline__ void hand_out(const double g0, const double g1, F &f, lane_seq<J...>) {
     (f(team_pick_ct<W, J>(g0), team_pick_ct<W, J>(g1)), ...);

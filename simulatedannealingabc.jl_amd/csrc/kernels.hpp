@@ -72,6 +72,19 @@ constexpr int update_block_threads(int s) { return s <= 1 ? SABC_UPDATE_BLOCK : 
 constexpr int update_min_waves(int s) {
   return s <= 1 ? SABC_UPDATE_MIN_WAVES : 3 * (cdf_coarse_entries(s) * s * 8 + 4096) <= 160 * 1024 ? SABC_UPDATE_MIN_WAVES_MS : SABC_UPDATE_MIN_WAVES;
 }
+// NormalStream's coop argument for the update kernels with a lane per particle: 0 = the trimmed simulate loop (device_rng.hpp:
+// for_pairs), kCoopPlainLoop = -1 = the plain one.  The exceptions are the instantiations in which the trimmed loop cost
+// occupancy or scratch (-S output of the compiler in use): kernels that sit on their register cap -- 80
+// VGPRs for 2-3 statistics (update_min_waves), 256 for the one-launch form of the models with many sums.
+constexpr bool update_loop_trimmed(int model, int d, int s, int prop, bool one_launch) {
+  if (one_launch) return model != 2 && model != 4;                                       // (SABC_MODEL_GAUSS2D, SABC_MODEL_LV)
+  if (model == 2 && prop != 0) return false;                                             // k_update<2,2,3,DE | Stretch>
+  if (model == 1 && d == 2 && s == 2 && prop == 1) return false;                         // k_update<1,2,2,DE>
+  return true;
+}
+constexpr int update_loop_coop(int model, int d, int s, int prop, bool one_launch) {
+  return update_loop_trimmed(model, d, s, prop, one_launch) ? 0 : -1;
+}
 // Simulators from source with more statistics than kNarrowStats (SABC_MAX_SOURCE_STATS = 64) take the WIDE form of the
 // per-particle kernels (update_kernel.hpp: k_update_wide, k_stats_wide, k_prior_simulate_wide, k_simulate_batch_wide; the distances
 // in LDS): the coarse ECDF index of 16 < s statistics does not fit the LDS, nor 1 + 2s + d + d(d+1)/2 sums the registers.

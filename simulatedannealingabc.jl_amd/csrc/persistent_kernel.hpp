@@ -261,7 +261,7 @@ k_update_persistent(const ModelDesc m, const PersistArgs pa, ControlBlock *cb, c
     SABC_TRACE(iter, 0);
     // RandomWalk ignores the inactive half (proposals.jl:40,52): one pass over the shard is the same update (engine.cpp)
     if (first_live) {
-      if (!have_draft) update_particle_draft<MODEL, D, S, PROP, kPast, LANES>(m, iter, pa.prop_p0, pa.prop_p1, &lcb, pp, pv_a, t, (uint64_t)(pp.gid0 + t), q);
+      if (!have_draft) update_particle_draft<MODEL, D, S, PROP, kPast, LANES, true>(m, iter, pa.prop_p0, pa.prop_p1, &lcb, pp, pv_a, t, (uint64_t)(pp.gid0 + t), q);
       update_particle_decide<D, S, kPast, LANES, true>(m, iter, &lcb, pp, cdf, cidx, t, (uint64_t)(pp.gid0 + t), q, acc);
     }
     have_draft = false;
@@ -318,7 +318,7 @@ k_update_persistent(const ModelDesc m, const PersistArgs pa, ControlBlock *cb, c
       if (ctrl_lane == 0) control_step_second<D, S>(lcb, a, blockIdx.x == 0 ? hist : nullptr, &cand, multi);
       SABC_TRACE(iter, 13);
     }
-    if (ahead && first_live) update_particle_draft<MODEL, D, S, PROP, kPast, LANES>(m, iter + 1, pa.prop_p0, pa.prop_p1, &lcb, pp, pv_a, t, (uint64_t)(pp.gid0 + t), q);
+    if (ahead && first_live) update_particle_draft<MODEL, D, S, PROP, kPast, LANES, true>(m, iter + 1, pa.prop_p0, pa.prop_p1, &lcb, pp, pv_a, t, (uint64_t)(pp.gid0 + t), q);
     have_draft = ahead;
     __syncthreads();
     SABC_TRACE(iter, 5);

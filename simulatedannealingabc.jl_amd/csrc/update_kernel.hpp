@@ -155,7 +155,7 @@ struct ParticleDraft {
 };
 
 // loads, proposal (:311), prior gate and simulation (:314-315)
-template <int MODEL, int D, int S, int PROP, bool PAST_CACHES, int LANES, class CB>
+template <int MODEL, int D, int S, int PROP, bool PAST_CACHES, int LANES, bool ONE_LAUNCH = false, class CB>
 __device__ __forceinline__ void update_particle_draft(const ModelDesc &m, const uint64_t iter, const double prop_p0, const double prop_p1,
                                                       const CB *__restrict__ cb, const PopPtrs &pp, const PartnerView &pv, const int64_t li,
                                                       const uint64_t gid, ParticleDraft<D, S> &q) {
@@ -220,7 +220,7 @@ __device__ __forceinline__ void update_particle_draft(const ModelDesc &m, const 
   for (int j = 0; j < S; ++j) q.rp[j] = 0.0;
   if (q.lpp > -INFINITY) {
     if (LANES > 1) Sim<MODEL, D, S>::run(m, q.thp, gid, iter, q.rp, LANES);    // :315
-    else Sim<MODEL, D, S>::run(m, q.thp, gid, iter, q.rp);
+    else Sim<MODEL, D, S>::run(m, q.thp, gid, iter, q.rp, update_loop_coop(MODEL, D, S, PROP, ONE_LAUNCH));
   }
   SABC_TRACE(iter, 8);
 }
@@ -287,7 +287,7 @@ __device__ __forceinline__ void update_particle(const ModelDesc &m, const uint64
                                                 const double (&cidx)[S][cdf_coarse_entries(S)], const int64_t li, const uint64_t gid,
                                                 double (&acc)[n_partials(D, S)]) {
   ParticleDraft<D, S> q;
-  update_particle_draft<MODEL, D, S, PROP, PAST_CACHES, LANES>(m, iter, prop_p0, prop_p1, cb, pp, pv, li, gid, q);
+  update_particle_draft<MODEL, D, S, PROP, PAST_CACHES, LANES, LATENCY>(m, iter, prop_p0, prop_p1, cb, pp, pv, li, gid, q);
   update_particle_decide<D, S, PAST_CACHES, LANES, LATENCY>(m, iter, cb, pp, cdf, cidx, li, gid, q, acc);
 }
 
