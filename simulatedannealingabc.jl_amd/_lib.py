@@ -207,6 +207,7 @@ def bind(L, strict=True):
         "sabc_comm_p2p_inject_loss": ([vp, C.c_int32], C.c_int),
         "sabc_comm_p2p_set_destroy_wait": ([vp, C.c_double], C.c_int),
         "sabc_comm_p2p_parked_bytes": ([], C.c_int64),
+        "sabc_debug_live_bytes": ([C.POINTER(C.c_int64)], C.c_int),
     }
     for name, (args, res) in sig.items():
         if not strict and not hasattr(L, name):

@@ -464,6 +464,11 @@ int sabc_comm_p2p_set_destroy_wait(sabc_handle *h, double milliseconds) {
 }
 
 int64_t sabc_comm_p2p_parked_bytes(void) { return HipBackend::parked_bytes(); }
+// device and pinned bytes that DeviceBuffer / MappedHostBuffer own right now (device_buffer.hpp); parked memory is not among them
+__attribute__((visibility("default"))) int sabc_debug_live_bytes(int64_t out[2]) {
+  out[0] = g_live_bytes[0].load(); out[1] = g_live_bytes[1].load();
+  return 0;
+}
 int64_t sabc_persistent_launches(const sabc_handle *h) { return h ? h->eng->persistent_launches() : 0; }
 int32_t sabc_persistent_lanes(const sabc_handle *h) { return h ? h->eng->persistent_lanes() : 0; }
 int64_t sabc_persistent_fallbacks(const sabc_handle *h) { return h ? h->eng->persistent_fallbacks() : 0; }
@@ -566,28 +571,27 @@ int sabc_op_build_cdf(int32_t device, const double *x, int64_t n, double *knots_
   if (rc) { g_err = why; return rc; }
   if (n < 1) { g_err = "empty input"; return SABC_ERR_EMPTY_CDF; }
   if (hipSetDevice(device) != hipSuccess) { g_err = "hipSetDevice failed"; return SABC_ERR_HIP; }
-  double *a = nullptr, *b = nullptr, *k = nullptr;
-  int64_t *meta = nullptr;
-  void *tmp = nullptr;
+  DeviceBuffer<double> a, b, k;
+  DeviceBuffer<int64_t> meta;
+  DeviceBuffer<char> tmp;
   size_t bytes = 0;
-  hipError_t e = hipMalloc((void **)&a, (size_t)n * 8);
-  if (e == hipSuccess) e = hipMalloc((void **)&b, (size_t)n * 8);
-  if (e == hipSuccess) e = hipMalloc((void **)&k, (size_t)(n + 2) * 8);
-  if (e == hipSuccess) e = hipMalloc((void **)&meta, 16);
-  if (e == hipSuccess) e = (hipError_t)sort_f64(a, b, n, nullptr, &bytes, nullptr);
-  if (e == hipSuccess) e = hipMalloc(&tmp, bytes ? bytes : 16);
-  if (e == hipSuccess) e = hipMemcpy(a, x, (size_t)n * 8, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = (hipError_t)sort_f64(a, b, n, tmp, &bytes, nullptr);
-  if (e == hipSuccess) e = (hipError_t)launch_cdf_knots(b, n, k, meta, nullptr);
+  hipError_t e = a.alloc((size_t)n);
+  if (e == hipSuccess) e = b.alloc((size_t)n);
+  if (e == hipSuccess) e = k.alloc((size_t)n + 2);
+  if (e == hipSuccess) e = meta.alloc(2);
+  if (e == hipSuccess) e = (hipError_t)sort_f64(a.get(), b.get(), n, nullptr, &bytes, nullptr);
+  if (e == hipSuccess) e = tmp.alloc(bytes ? bytes : 16);
+  if (e == hipSuccess) e = hipMemcpy(a.get(), x, (size_t)n * 8, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = (hipError_t)sort_f64(a.get(), b.get(), n, tmp.get(), &bytes, nullptr);
+  if (e == hipSuccess) e = (hipError_t)launch_cdf_knots(b.get(), n, k.get(), meta.get(), nullptr);
   int64_t hm[2] = {0, 0};
-  if (e == hipSuccess) e = hipMemcpy(hm, meta, 16, hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = hipMemcpy(hm, meta.get(), 16, hipMemcpyDeviceToHost);
   int64_t len = 0;
   if (e == hipSuccess) {
     const int64_t mpos = n - hm[0];
     len = mpos > 0 ? mpos + 2 : 0;
-    if (len) e = hipMemcpy(knots_out, k, (size_t)len * 8, hipMemcpyDeviceToHost);
+    if (len) e = hipMemcpy(knots_out, k.get(), (size_t)len * 8, hipMemcpyDeviceToHost);
   }
-  (void)hipFree(a); (void)hipFree(b); (void)hipFree(k); (void)hipFree(meta); (void)hipFree(tmp);
   if (e != hipSuccess) { g_err = hipGetErrorString(e); return SABC_ERR_HIP; }
   if (hm[1]) { g_err = "Negative distances are not allowed!"; return SABC_ERR_NEG_DISTANCE; }
   if (!len) { g_err = "no positive entry"; return SABC_ERR_EMPTY_CDF; }
@@ -601,17 +605,16 @@ int sabc_op_sort(int32_t device, const double *x, int64_t n, double *out) {
   if (rc) { g_err = why; return rc; }
   if (n <= 0) return 0;
   if (hipSetDevice(device) != hipSuccess) { g_err = "hipSetDevice failed"; return SABC_ERR_HIP; }
-  double *a = nullptr, *b = nullptr;
-  void *tmp = nullptr;
+  DeviceBuffer<double> a, b;
+  DeviceBuffer<char> tmp;
   size_t bytes = 0;
-  hipError_t e = hipMalloc((void **)&a, (size_t)n * 8);
-  if (e == hipSuccess) e = hipMalloc((void **)&b, (size_t)n * 8);
-  if (e == hipSuccess) e = (hipError_t)sort_f64(a, b, n, nullptr, &bytes, nullptr);
-  if (e == hipSuccess) e = hipMalloc(&tmp, bytes ? bytes : 16);
-  if (e == hipSuccess) e = hipMemcpy(a, x, (size_t)n * 8, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = (hipError_t)sort_f64(a, b, n, tmp, &bytes, nullptr);
-  if (e == hipSuccess) e = hipMemcpy(out, b, (size_t)n * 8, hipMemcpyDeviceToHost);
-  (void)hipFree(a); (void)hipFree(b); (void)hipFree(tmp);
+  hipError_t e = a.alloc((size_t)n);
+  if (e == hipSuccess) e = b.alloc((size_t)n);
+  if (e == hipSuccess) e = (hipError_t)sort_f64(a.get(), b.get(), n, nullptr, &bytes, nullptr);
+  if (e == hipSuccess) e = tmp.alloc(bytes ? bytes : 16);
+  if (e == hipSuccess) e = hipMemcpy(a.get(), x, (size_t)n * 8, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = (hipError_t)sort_f64(a.get(), b.get(), n, tmp.get(), &bytes, nullptr);
+  if (e == hipSuccess) e = hipMemcpy(out, b.get(), (size_t)n * 8, hipMemcpyDeviceToHost);
   if (e != hipSuccess) { g_err = hipGetErrorString(e); return SABC_ERR_HIP; }
   return 0;
 }
@@ -623,15 +626,14 @@ int sabc_op_cdf_eval(int32_t device, const double *knots, int64_t len, const dou
   if (len < 2 || m < 0) { g_err = "bad length"; return SABC_ERR_BAD_CONFIG; }
   if (m == 0) return 0;
   if (hipSetDevice(device) != hipSuccess) { g_err = "hipSetDevice failed"; return SABC_ERR_HIP; }
-  double *k = nullptr, *dq = nullptr, *dout = nullptr;
-  hipError_t e = hipMalloc((void **)&k, (size_t)len * 8);
-  if (e == hipSuccess) e = hipMalloc((void **)&dq, (size_t)m * 8);
-  if (e == hipSuccess) e = hipMalloc((void **)&dout, (size_t)m * 8);
-  if (e == hipSuccess) e = hipMemcpy(k, knots, (size_t)len * 8, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(dq, q, (size_t)m * 8, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = (hipError_t)launch_cdf_eval(k, len, dq, m, dout, nullptr);
-  if (e == hipSuccess) e = hipMemcpy(out, dout, (size_t)m * 8, hipMemcpyDeviceToHost);
-  (void)hipFree(k); (void)hipFree(dq); (void)hipFree(dout);
+  DeviceBuffer<double> k, dq, dout;
+  hipError_t e = k.alloc((size_t)len);
+  if (e == hipSuccess) e = dq.alloc((size_t)m);
+  if (e == hipSuccess) e = dout.alloc((size_t)m);
+  if (e == hipSuccess) e = hipMemcpy(k.get(), knots, (size_t)len * 8, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(dq.get(), q, (size_t)m * 8, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = (hipError_t)launch_cdf_eval(k.get(), len, dq.get(), m, dout.get(), nullptr);
+  if (e == hipSuccess) e = hipMemcpy(out, dout.get(), (size_t)m * 8, hipMemcpyDeviceToHost);
   if (e != hipSuccess) { g_err = hipGetErrorString(e); return SABC_ERR_HIP; }
   return 0;
 }
@@ -662,14 +664,13 @@ int sabc_op_philox(int32_t device, uint64_t seed, uint64_t pid, uint32_t purpose
   int rc = usable_device(device, why);
   if (rc) { g_err = why; return rc; }
   if (hipSetDevice(device) != hipSuccess) { g_err = "hipSetDevice failed"; return SABC_ERR_HIP; }
-  uint32_t *w = nullptr;
-  double *z = nullptr;
-  hipError_t e = hipMalloc((void **)&w, 16);
-  if (e == hipSuccess) e = hipMalloc((void **)&z, 16);
-  if (e == hipSuccess) e = (hipError_t)launch_philox_debug(seed, pid, purpose, iter, k, w, z, nullptr);
-  if (e == hipSuccess) e = hipMemcpy(out_words, w, 16, hipMemcpyDeviceToHost);
-  if (e == hipSuccess) e = hipMemcpy(out_normals, z, 16, hipMemcpyDeviceToHost);
-  (void)hipFree(w); (void)hipFree(z);
+  DeviceBuffer<uint32_t> w;
+  DeviceBuffer<double> z;
+  hipError_t e = w.alloc(4);
+  if (e == hipSuccess) e = z.alloc(2);
+  if (e == hipSuccess) e = (hipError_t)launch_philox_debug(seed, pid, purpose, iter, k, w.get(), z.get(), nullptr);
+  if (e == hipSuccess) e = hipMemcpy(out_words, w.get(), 16, hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = hipMemcpy(out_normals, z.get(), 16, hipMemcpyDeviceToHost);
   if (e != hipSuccess) { g_err = hipGetErrorString(e); return SABC_ERR_HIP; }
   return 0;
 }
@@ -681,11 +682,10 @@ int sabc_op_normal_pairs(int32_t device, uint64_t seed, uint64_t pid0, uint32_t 
   if (rc) { g_err = why; return rc; }
   if (m <= 0) return 0;
   if (hipSetDevice(device) != hipSuccess) { g_err = "hipSetDevice failed"; return SABC_ERR_HIP; }
-  double *d = nullptr;
-  hipError_t e = hipMalloc((void **)&d, (size_t)m * 16);
-  if (e == hipSuccess) e = (hipError_t)launch_normal_pairs(seed, pid0, purpose, iter, k, m, d, nullptr);
-  if (e == hipSuccess) e = hipMemcpy(out_2m, d, (size_t)m * 16, hipMemcpyDeviceToHost);
-  (void)hipFree(d);
+  DeviceBuffer<double> d;
+  hipError_t e = d.alloc(2 * (size_t)m);
+  if (e == hipSuccess) e = (hipError_t)launch_normal_pairs(seed, pid0, purpose, iter, k, m, d.get(), nullptr);
+  if (e == hipSuccess) e = hipMemcpy(out_2m, d.get(), (size_t)m * 16, hipMemcpyDeviceToHost);
   if (e != hipSuccess) { g_err = hipGetErrorString(e); return SABC_ERR_HIP; }
   return 0;
 }
@@ -696,21 +696,20 @@ int sabc_op_rng_peak(int32_t device, int64_t n_lanes, int32_t pairs_per_lane, in
   if (rc) { g_err = why; return rc; }
   if (n_lanes < 1 || pairs_per_lane < 1 || repeats < 1) { g_err = "bad arguments"; return SABC_ERR_BAD_CONFIG; }
   if (hipSetDevice(device) != hipSuccess) { g_err = "hipSetDevice failed"; return SABC_ERR_HIP; }
-  double *d = nullptr;
+  DeviceBuffer<double> d;
   hipEvent_t a = nullptr, b = nullptr;
-  hipError_t e = hipMalloc((void **)&d, (size_t)n_lanes * 8);
+  hipError_t e = d.alloc((size_t)n_lanes);
   if (e == hipSuccess) e = hipEventCreate(&a);
   if (e == hipSuccess) e = hipEventCreate(&b);
-  if (e == hipSuccess) e = (hipError_t)launch_rng_peak(1, pairs_per_lane, n_lanes, d, nullptr);   // warm-up
+  if (e == hipSuccess) e = (hipError_t)launch_rng_peak(1, pairs_per_lane, n_lanes, d.get(), nullptr);   // warm-up
   if (e == hipSuccess) e = hipEventRecord(a, nullptr);
-  for (int r = 0; r < repeats && e == hipSuccess; ++r) e = (hipError_t)launch_rng_peak(2 + r, pairs_per_lane, n_lanes, d, nullptr);
+  for (int r = 0; r < repeats && e == hipSuccess; ++r) e = (hipError_t)launch_rng_peak(2 + r, pairs_per_lane, n_lanes, d.get(), nullptr);
   if (e == hipSuccess) e = hipEventRecord(b, nullptr);
   if (e == hipSuccess) e = hipEventSynchronize(b);
   float ms = 0.f;
   if (e == hipSuccess) e = hipEventElapsedTime(&ms, a, b);
   if (a) (void)hipEventDestroy(a);
   if (b) (void)hipEventDestroy(b);
-  (void)hipFree(d);
   if (e != hipSuccess) { g_err = hipGetErrorString(e); return SABC_ERR_HIP; }
   *normals_per_s = 2.0 * (double)pairs_per_lane * (double)n_lanes * (double)repeats / ((double)ms * 1e-3);
   return 0;

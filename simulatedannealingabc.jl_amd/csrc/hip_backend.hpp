@@ -9,6 +9,7 @@
 #include "engine.hpp"
 #include "kernels.hpp"
 #include "p2p_page.hpp"
+#include "device_buffer.hpp"
 
 namespace sabc {
 
@@ -18,17 +19,17 @@ class HipBackend : public Backend {
   ~HipBackend() override;
 
   int allocate(const ModelDesc &m, const Shard &sh) override;
-  double *pop_block() override { return pop_[cur_]; }
-  double *rho_block() override { return rho_; }
+  double *pop_block() override { return pop_[cur_].get(); }
+  double *rho_block() override { return rho_.get(); }
   double *sums_buffer() override;
   double *gather_buffer(int64_t doubles) override;
   double *scratch_buffer(int which, int64_t doubles) override;
   int copy_rows(const double *src, int64_t src_pitch, double *dst, int64_t dst_pitch, int rows, int64_t count) override;
   int to_backend(double *dst, const double *src_host, int64_t n) override;
   int to_host(double *dst_host, const double *src, int64_t n) override;
-  int set_host_simulator(sabc_simulate_fn fn, void *ctx) override { host_fn_ = fn; host_ctx_ = ctx; return 0; }
+  int set_host_simulator(sabc_simulate_fn fn, void *ctx) override { host_.fn = fn; host_.ctx = ctx; return 0; }
   int set_host_prior(sabc_prior_sample_fn sample, sabc_prior_logpdf_fn logpdf, void *ctx) override {
-    prior_sample_fn_ = sample; prior_logpdf_fn_ = logpdf; prior_ctx_ = ctx;
+    host_.prior_sample_fn = sample; host_.prior_logpdf_fn = logpdf; host_.prior_ctx = ctx;
     return 0;
   }
   // SABC_MODEL_USER: compile the simulator source into the update kernels (rtc.hpp); the compiler log goes to error()
@@ -42,7 +43,7 @@ class HipBackend : public Backend {
   int update_range(const StepArgs &c, const PartnerView &pv, int64_t lo, int64_t cnt, int64_t row0,
                    int64_t *rows_out) override;
   bool persistent_supported(int prop_kind) const override;
-  int persistent_lanes() const override { return persist_lanes_; }
+  int persistent_lanes() const override { return persist_.lanes; }
   int update_persistent(const StepArgs &c, const ControlArgs &ctrl, const PartnerView &pv_a, const PartnerView &pv_b, int64_t ix0,
                         int64_t phase, int64_t cph, int64_t count, int64_t *done, int *halted, int *error) override;
   int stats(int64_t *rows_out) override;
@@ -71,8 +72,8 @@ class HipBackend : public Backend {
   int set_knots(int stat, const double *knots, int64_t len) override;
 
   // peer-to-peer transport (p2p.hpp)
-  bool p2p_active() const override { return p2p_on_; }
-  int p2p_exchange_pending() override { pending_xchg_ = true; return 0; }
+  bool p2p_active() const override { return p2p_.on; }
+  int p2p_exchange_pending() override { p2p_.pending_xchg = true; return 0; }
   int p2p_barrier(bool guarded) override;
   int p2p_commit(int status, bool wait) override;
   void p2p_disable() override { (void)p2p_leave(); }
@@ -87,21 +88,21 @@ class HipBackend : public Backend {
   int p2p_selftest();
   int p2p_leave();                                  // p2p.hpp "LEAVES": leaving -> leave words -> drain -> unmap -> released
   // the group has agreed that every shard has left and unmapped (p2p_setup.hpp): nothing exported is mapped anywhere
-  void p2p_forget_export() { if (!mapped_) exported_ = false; }
-  void p2p_set_destroy_wait(double ms) { destroy_wait_ms_ = ms; }
-  void p2p_inject_stale(int n) { p2p_stale_ = n > 0 ? n : 0; }
+  void p2p_forget_export() { if (!p2p_.mapped) p2p_.exported = false; }
+  void p2p_set_destroy_wait(double ms) { p2p_.destroy_wait_ms = ms; }
+  void p2p_inject_stale(int n) { p2p_.stale = n > 0 ? n : 0; }
   static int64_t parked_bytes();
-  void p2p_set_timeout(double ms) { if (ms > 0) p2p_timeout_ms_ = ms; }
+  void p2p_set_timeout(double ms) { if (ms > 0) p2p_.timeout_ms = ms; }
   // test hook: n > 0: the next n posts are skipped; n < 0: -n more posts go out, then one is skipped
-  void p2p_inject_silence(int n) { p2p_loss_ = false; if (n >= 0) { p2p_skip_ = 0; p2p_silent_ = n; } else { p2p_skip_ = -n; p2p_silent_ = 1; } }
+  void p2p_inject_silence(int n) { p2p_.loss = false; if (n >= 0) { p2p_.skip = 0; p2p_.silent = n; } else { p2p_.skip = -n; p2p_.silent = 1; } }
   // test hook: n more posts go out, then one reaches only this shard's OWN slots (a post lost on the wire: the shard itself
   // carries on with its peers' rows, they run into the bound)
-  void p2p_inject_loss(int n) { p2p_loss_ = true; p2p_skip_ = n > 0 ? n : 0; p2p_silent_ = 1; }
+  void p2p_inject_loss(int n) { p2p_.loss = true; p2p_.skip = n > 0 ? n : 0; p2p_.silent = 1; }
   int64_t kernel_launches() const { return launches_; }
   // host-simulator mode: seconds spent inside the caller's callbacks so far / calls of f_dist; particles per chunk
-  double host_callback_seconds() const { return host_cb_seconds_; }
-  int64_t host_callback_calls() const { return host_cb_calls_; }
-  void set_host_chunk(int64_t particles) { host_chunk_ = particles > 0 ? particles : 0; }
+  double host_callback_seconds() const { return host_.cb_seconds; }
+  int64_t host_callback_calls() const { return host_.cb_calls; }
+  void set_host_chunk(int64_t particles) { host_.chunk = particles > 0 ? particles : 0; }
 
   // extras used by the C-ABI layer
   int set_stream(hipStream_t s);
@@ -122,122 +123,142 @@ class HipBackend : public Backend {
   int check(hipError_t e, const char *what);
   PopPtrs pop_ptrs(int which) const;
 
+  // Declaration order is release order, backwards: after ~HipBackend() has left the group and drained the stream, the
+  // buffers below are freed, then the run-time compiled kernels are released, and the stream goes back to the pool last.
   int device_ = 0;
   hipStream_t stream_ = nullptr;
   bool own_stream_ = false;
-  char *pinned_block_ = nullptr;                          // one pinned, mapped allocation behind cb_host_, mbox_host_, totals_host_
+  struct StreamReturn { HipBackend *be; ~StreamReturn(); } stream_return_{this};
+  struct Rtc : RtcKernels { ~Rtc() { rtc_release(this); } } rtc_;   // SABC_MODEL_USER: kernels compiled from the user's source
+  const RtcKernels *rtc() const { return rtc_.module ? &rtc_ : nullptr; }
   std::string err_;
   ModelDesc m_{};
   Shard sh_{};
   int np_ = 0;
-  double *pop_[2] = {nullptr, nullptr};
+  DeviceBuffer<double> pop_[2];
   int cur_ = 0;
-  double *rho_ = nullptr, *knots_ = nullptr, *coarse_ = nullptr, *mid_ = nullptr;
+  DeviceBuffer<double> rho_, knots_, coarse_, mid_;
   int64_t mid_stride_ = 0;
   int32_t cdf_shift_[kMaxStats] = {0};
   int build_coarse(int stat);
   int64_t knot_stride_ = 0;
   int64_t cdf_len_[kMaxStats] = {0};
-  double *partials_ = nullptr;
+  DeviceBuffer<double> partials_;
   int64_t partial_rows_ = 0;
-  ControlBlock *cb_dev_ = nullptr, *cb_host_ = nullptr;   // device block + pinned staging copy
-  Mailbox *mbox_host_ = nullptr, *mbox_dev_ = nullptr;    // pinned + mapped: device posts, host polls
-  double *hist_dev_ = nullptr;
+  // ONE pinned, mapped allocation (hipHostFree is 0.2 ms apiece) and the views into it: the control block's staging copy, the
+  // mailbox ring the device posts to and the host polls, and where k_scan_offsets posts (sum w, sum w^2)
+  MappedHostBuffer<char> pinned_;
+  ControlBlock *cb_host_ = nullptr;
+  Mailbox *mbox_host_ = nullptr, *mbox_dev_ = nullptr;
+  double *totals_host_ = nullptr, *totals_host_dev_ = nullptr;
+  DeviceBuffer<ControlBlock> cb_dev_;
+  DeviceBuffer<double> hist_dev_;
   int flush_reduce();                                     // launch a deferred k_reduce_partials
   int64_t pending_rows_ = -1;                             // >= 0: a reduction waits to be fused into k_control
   int64_t fuse_reduce_max_ = kFuseReduceMaxDoubles;       // partial-row matrices up to this many doubles: reduced inside the control launch
   bool pending_guarded_ = false;
-  double *sums_stage_ = nullptr;                          // reduction / allreduce target, taken over by k_control
+  DeviceBuffer<double> sums_stage_;                       // reduction / allreduce target, taken over by k_control
   int64_t hist_cap_ = 0;
-  double *gather_ = nullptr;
-  int64_t gather_cap_ = 0;
-  double *scratch_[4] = {nullptr, nullptr, nullptr, nullptr};
-  int64_t scratch_cap_[4] = {0, 0, 0, 0};
-  int64_t *idx_dev_ = nullptr, *slot_dev_ = nullptr;      // sharded resample: drawn source indices, reply -> destination
-  unsigned long long *bucket_dev_ = nullptr;              // [2][world]: counts, cursors
-  unsigned long long *bucket_host_ = nullptr;             // pinned staging of the same
-  double *cum_ = nullptr, *block_sums_ = nullptr, *totals_dev_ = nullptr;
-  double *totals_host_ = nullptr, *totals_host_dev_ = nullptr;   // pinned + mapped: k_scan_offsets posts (sum w, sum w^2) there
-  double *pack_dev_ = nullptr;                                   // one shard: packed resample lines (kernels.hpp: launch_resample_local)
-  double *col_a_ = nullptr, *col_b_ = nullptr;
-  void *sort_tmp_ = nullptr;
+  DeviceBuffer<double> gather_, scratch_[4];
+  DeviceBuffer<int64_t> idx_dev_, slot_dev_;              // sharded resample: drawn source indices, reply -> destination
+  DeviceBuffer<unsigned long long> bucket_dev_;           // [2][world]: counts, cursors
+  MappedHostBuffer<unsigned long long> bucket_host_;      // pinned staging of the same
+  DeviceBuffer<double> cum_, block_sums_, totals_dev_;
+  DeviceBuffer<double> pack_dev_;                         // one shard: packed resample lines (kernels.hpp: launch_resample_local)
+  DeviceBuffer<double> col_a_, col_b_;
+  DeviceBuffer<char> sort_tmp_;
   size_t sort_tmp_bytes_ = 0;
-  int64_t *meta_dev_ = nullptr;
+  DeviceBuffer<int64_t> meta_dev_;
   std::vector<double> stage_;
-  // host-simulator mode
-  sabc_simulate_fn host_fn_ = nullptr;
-  sabc_prior_sample_fn prior_sample_fn_ = nullptr;      // prior_joint = 2: rand(prior) / logpdf(prior, .) on the host
-  sabc_prior_logpdf_fn prior_logpdf_fn_ = nullptr;
-  void *prior_ctx_ = nullptr;
-  void *host_ctx_ = nullptr;
-  // staging of a half batch: pinned host arrays (host_x_) mapped into the device (host_x_dev_), allocated once
-  double *host_thp_ = nullptr, *host_rho_ = nullptr, *host_cur_ = nullptr, *host_lp2_ = nullptr;
-  double *host_thp_dev_ = nullptr, *host_rho_dev_ = nullptr, *host_cur_dev_ = nullptr, *host_lp2_dev_ = nullptr;
-  unsigned char *host_gate_ = nullptr, *host_gate_dev_ = nullptr;      // one byte per proposal: inside the prior's support?
-  double *dev_thp_ = nullptr, *dev_aux_ = nullptr;                     // device memory: proposals, (log prior, log factor)
-  double *dev_rho_prop_ = nullptr;                                     // ... and, for a device-coded simulator next to a host prior, their distances
+  void free_later(void *p);                               // device memory released by end_of_call(), never inside a call
+  std::vector<void *> deferred_free_;
+  // a buffer that has to grow inside a call: the old allocation goes to the deferred list, never to hipFree
+  template <class T>
+  hipError_t grow(DeviceBuffer<T> &b, size_t count) {
+    if (stream_) (void)hipStreamSynchronize(stream_);
+    free_later(b.release());
+    return b.alloc(count);
+  }
+
+  // host-simulator mode (hip_backend_hostmode.hip)
   static constexpr int kHostMaxChunks = 64;
-  unsigned long long *host_flag_ = nullptr, *host_flag_dev_ = nullptr;   // per chunk: the proposal kernel posts, the host polls
-  unsigned int *host_done_dev_ = nullptr;
-  unsigned long long host_seq_ = 0;
-  int64_t host_chunk_ = 0;                                // particles per chunk; 0 = automatic (host_chunk_size)
-  std::vector<int64_t> host_ids_, host_where_;
-  std::vector<double> host_thv_, host_rhov_, host_both_, host_lp_;
-  double host_cb_seconds_ = 0.0;                          // time spent inside the caller's callbacks
-  int64_t host_cb_calls_ = 0;
-  unsigned long long *host_acc_dev_ = nullptr;
+  struct HostMode {
+    sabc_simulate_fn fn = nullptr;
+    sabc_prior_sample_fn prior_sample_fn = nullptr;      // prior_joint = 2: rand(prior) / logpdf(prior, .) on the host
+    sabc_prior_logpdf_fn prior_logpdf_fn = nullptr;
+    void *prior_ctx = nullptr;
+    void *ctx = nullptr;
+    struct Staging {                                      // allocated once, all or nothing (ensure_host_buffers)
+      // a half batch in pinned host arrays mapped into the device
+      MappedHostBuffer<double> thp, rho, cur, lp2;
+      MappedHostBuffer<unsigned char> gate;               // one byte per proposal: inside the prior's support?
+      DeviceBuffer<double> dev_thp, dev_aux;              // device memory: proposals, (log prior, log factor)
+      DeviceBuffer<double> dev_rho_prop;                  // ... and, for a device-coded simulator next to a host prior, their distances
+      MappedHostBuffer<unsigned long long> flag;          // per chunk: the proposal kernel posts, the host polls
+      DeviceBuffer<unsigned int> done;
+      DeviceBuffer<unsigned long long> acc;
+    } buf;
+    unsigned long long seq = 0;
+    int64_t chunk = 0;                                    // particles per chunk; 0 = automatic (host_chunk_size)
+    std::vector<int64_t> ids, where;
+    std::vector<double> thv, rhov, both, lp;
+    double cb_seconds = 0.0;                              // time spent inside the caller's callbacks
+    int64_t cb_calls = 0;
+  } host_;
   int ensure_host_buffers();
   int64_t host_chunk_size(int64_t cnt) const;
   int wait_host_flag(int ch, unsigned long long seq);
-  RtcKernels rtc_;                                        // SABC_MODEL_USER: kernels compiled from the user's source
-  const RtcKernels *rtc() const { return rtc_.module ? &rtc_ : nullptr; }
-  void free_later(void *p);                               // device memory released by end_of_call(), never inside a call
-  std::vector<void *> deferred_free_;
-  // peer-to-peer transport
+
+  // peer-to-peer transport (hip_backend_p2p.hip)
+  struct P2P {
+    DeviceBuffer<uint64_t> slots;                         // this shard's slot area (fine-grained device memory)
+    uint64_t *peer_slots[kMaxPeers] = {nullptr};
+    double *peer_pop[2][kMaxPeers] = {{nullptr}};
+    double *peer_rho[kMaxPeers] = {nullptr};
+    int peer_cur0[kMaxPeers] = {0};                       // the owner's parity when the descriptors were written
+    uint32_t flips = 0;                                   // buffer flips of THIS shard since then (in step on all shards)
+    std::vector<void *> ipc_opened;                       // what hipIpcOpenMemHandle returned (closed when this shard leaves)
+    P2PHostPage *page = nullptr;                          // this shard's host page (POSIX shared memory)
+    char page_name[48] = {0};
+    const P2PHostPage *peer_page[kMaxPeers] = {nullptr};
+    bool peer_page_shm[kMaxPeers] = {false};              // opened by name (to be unmapped), not a pointer of this process
+    uint32_t gen = 0;                                     // generation of the current (or last) set-up
+    bool mapped = false;                                  // the peers' memory is mapped
+    bool exported = false;                                // a descriptor has left: peers may have mapped this shard's memory
+    double destroy_wait_ms = -1.0;                        // < 0: the bound of the waits
+    int stale = 0;
+    bool on = false, pending_xchg = false;
+    uint32_t xseq = 0, bseq = 0, call = 0;                // exchange / barrier / call sequence numbers (the same on every shard)
+    double timeout_ms = 5000.0;
+    int silent = 0, skip = 0;
+    bool loss = false;
+    DeviceBuffer<double> test_dev;
+    DeviceBuffer<double> snap_pop, snap_rho;              // device-side copy of the particles at the entry of a call
+  } p2p_;
   int build_cdf_blocks(const ShardBlocks &rho_blocks, int64_t *len_out, int *any_negative);
   P2PView p2p_view() const;
   int take_silence() {                                    // 0 | 1 skipped | 2 own slots only
-    if (p2p_skip_ > 0) { --p2p_skip_; return 0; }
-    if (p2p_silent_ > 0) { --p2p_silent_; return p2p_loss_ ? 2 : 1; }
+    if (p2p_.skip > 0) { --p2p_.skip; return 0; }
+    if (p2p_.silent > 0) { --p2p_.silent; return p2p_.loss ? 2 : 1; }
     return 0;
   }
   bool p2p_finish();                                      // destructor: leave, wait for the peers' `released`; false = park
-  void flip_cur() { cur_ = 1 - cur_; ++flips_; if (page_) page_->cur_parity.store((uint32_t)cur_, std::memory_order_relaxed); }
+  void flip_cur() { cur_ = 1 - cur_; ++p2p_.flips; if (p2p_.page) p2p_.page->cur_parity.store((uint32_t)cur_, std::memory_order_relaxed); }
   // a peer's CURRENT population: indexed by the owner's parity at set-up + the flips since (p2p.hpp: P2PDesc::cur)
-  double *peer_pop_cur(int r) const { return peer_pop_[(peer_cur0_[r] ^ (int)(flips_ & 1u)) & 1][r]; }
-  uint32_t tag(uint32_t seq) const { return p2p_tag(gen_, seq); }
+  double *peer_pop_cur(int r) const { return p2p_.peer_pop[(p2p_.peer_cur0[r] ^ (int)(p2p_.flips & 1u)) & 1][r]; }
+  uint32_t tag(uint32_t seq) const { return p2p_tag(p2p_.gen, seq); }
   int selftest_patterns(const P2PView &pv);
   bool open_peer_page(int r, const P2PDesc &d);
-  uint64_t *slots_ = nullptr;                             // this shard's slot area (fine-grained device memory)
-  uint64_t *peer_slots_[kMaxPeers] = {nullptr};
-  double *peer_pop_[2][kMaxPeers] = {{nullptr}};
-  double *peer_rho_[kMaxPeers] = {nullptr};
-  int peer_cur0_[kMaxPeers] = {0};                        // the owner's parity when the descriptors were written
-  uint32_t flips_ = 0;                                    // buffer flips of THIS shard since then (in step on all shards)
-  std::vector<void *> ipc_opened_;                        // what hipIpcOpenMemHandle returned (closed when this shard leaves)
-  P2PHostPage *page_ = nullptr;                           // this shard's host page (POSIX shared memory)
-  char page_name_[48] = {0};
-  const P2PHostPage *peer_page_[kMaxPeers] = {nullptr};
-  bool peer_page_shm_[kMaxPeers] = {false};               // opened by name (to be unmapped), not a pointer of this process
-  uint32_t gen_ = 0;                                      // generation of the current (or last) set-up
-  bool mapped_ = false;                                   // the peers' memory is mapped
-  bool exported_ = false;                                 // a descriptor has left: peers may have mapped this shard's memory
-  double destroy_wait_ms_ = -1.0;                         // < 0: the bound of the waits
-  int p2p_stale_ = 0;
-  bool p2p_on_ = false, pending_xchg_ = false;
-  uint32_t xseq_ = 0, bseq_ = 0, call_ = 0;               // exchange / barrier / call sequence numbers (the same on every shard)
-  double p2p_timeout_ms_ = 5000.0;
+
   int wall_clock_khz_ = 100000;                           // s_memrealtime: 100 MHz unless the device says otherwise
-  int p2p_silent_ = 0, p2p_skip_ = 0;
-  bool p2p_loss_ = false;
-  double *p2p_test_dev_ = nullptr;
-  double *snap_pop_ = nullptr, *snap_rho_ = nullptr;     // device-side copy of the particles at the entry of a call
   int64_t launches_ = 0;
-  int64_t persist_max_ = 65536;                           // shards up to this many particles run their updates in one launch (0: never)
-  unsigned long long *persist_sync_ = nullptr;            // the grid barrier's counter and abort flag
-  unsigned long long *persist_rows_ = nullptr;            // the workgroups' partial rows as tagged words, two parities (persistent_kernel.hpp)
-  int64_t persist_rows_wg_ = 0;                           // workgroups it holds rows for
-  int persist_lanes_ = 0;                                 // lanes per particle of the last one-launch update (0: none yet)
+  struct Persist {                                        // the one-launch form of small shards (persistent_kernel.hpp)
+    int64_t max = 65536;                                  // shards up to this many particles run their updates in one launch (0: never)
+    DeviceBuffer<unsigned long long> sync;                // the grid barrier's counter and abort flag
+    DeviceBuffer<unsigned long long> rows;                // the workgroups' partial rows as tagged words, two parities
+    int64_t rows_wg = 0;                                  // workgroups it holds rows for
+    int lanes = 0;                                        // lanes per particle of the last one-launch update (0: none yet)
+  } persist_;
   int prof_ = 0, prof_open_ = -1;
   unsigned prof_tick_ = 0;
   struct EvPair { hipEvent_t a, b; };

@@ -466,6 +466,7 @@ def test_p2p_self_test_leaves_live_populations_untouched(S, gpu):
             torch.cuda.set_device(0)
             model, prior = hip_model_prior(S, "gauss2d_cfg3")
             h = S.SabcHandle(n_particles=n, model=model, prior=prior, seed=SEED, rank=rank, world=2)
+            h.set_stream(shard_stream(rank))      # shards of one device in one process: never on one hardware queue (see above)
             for attempt in range(2):
                 descs[rank] = h.p2p_descriptor()
                 barrier.wait()
