@@ -201,6 +201,19 @@ SABC_API int64_t     sabc_host_callback_calls(const sabc_handle *h);
    (a function of its arguments and its draws alone.  for_pairs is the loop to draw the bulk of a simulation with: a small
    population runs a call's updates in one launch with a TEAM of 4 or 16 lanes per particle, which then generate 16 or 64
    pairs at a time, four blocks per lane -- csrc/device_rng.hpp; the stream is the same stream however it is drawn.)
+   Discrete-event and count models (Gillespie, tau-leaping, chain-binomial) draw WHOLE blocks of the same stream, (u0, u1)
+   being the uniforms uniform_pair() would have returned for the block:
+       rng.exponential_pair(e0, e1)    one block: e_i = -log(u_i)
+       rng.event_pair(e, u)            one block: e = -log(u0), u = u1 -- waiting time and event choice of one Gillespie step
+       rng.while_events(max_events, [&](double e, double u) { ...; return go_on; })
+                                       the event pairs of successive blocks until the lambda returns false or max_events
+                                       calls are made (the bound is mandatory); returns the number of calls = blocks consumed.
+                                       A team generates a group of 4 | 16 events side by side and drops the rest at the
+                                       first false: the loop for a trip count that depends on the draws
+       rng.poisson(lambda)             <= 0: 0, no block | < 10: inversion, one block | else Hoermann's PTRS, a block per
+                                       trial (at most 64); lambda <= 2^30
+       rng.binomial(n, p)              n <= 0 or p <= 0: 0, p >= 1: n, no block | n min(p, 1 - p) < 10: inversion, one block |
+                                       else Hoermann's BTRS, a block per trial (at most 64)
    With sabc_config::prior_joint = 3 the same source also defines the PRIOR -- any distribution, evaluated inside the fused
    kernel (SimulatedAnnealingABC.jl:151 takes any Distributions.Distribution):
        __device__ void   sabc_user_prior_sample(const double *params, sabc::NormalStream &rng, double *theta_out);

@@ -247,6 +247,21 @@ __device__ __forceinline__ double tanh_abs_tab(double y) {
   return copysign(t, y);
 }
 
+// log(k!) = lgamma(k + 1) for an integer-valued k >= 0 (the count draws' acceptance tests; the library's lgamma is a long general
+// routine): k < 16 from a table, else Stirling's series in x = k + 1 >= 17 through 1/(1188 x^9) -- the first term left out is
+// below 6e-17 absolutely, so the error is the ulp or two of (x - 1/2) log x, as for the library routine
+static __device__ const double kLogFactorial[16] = {0.0, 0.0, 0.6931471805599453, 1.791759469228055, 3.1780538303479458, 4.787491742782046, 6.579251212010101, 8.525161361065415, 10.60460290274525, 12.801827480081469, 15.104412573075516, 17.502307845873887, 19.987214495661885, 22.552163853123425, 25.19122118273868, 27.89927138384089};
+__device__ __forceinline__ double log_factorial(const double k) {
+  if (k < 16.0) return kLogFactorial[(int)k];
+  const double x = k + 1.0, r = div_fast(1.0, x), r2 = r * r;
+  double p = 1.0 / 1188.0;
+  p = fma(p, r2, -1.0 / 1680.0);
+  p = fma(p, r2, 1.0 / 1260.0);
+  p = fma(p, r2, -1.0 / 360.0);
+  p = fma(p, r2, 1.0 / 12.0);
+  return fma(x - 0.5, log_fast(x), -x) + fma(p, r, 9.18938533204672741780e-01);      // + log(2 pi) / 2
+}
+
 __device__ __forceinline__ void box_muller(const u32x4 w, double &z0, double &z1) {
   const double ua = u52(w.x, w.y);
   const double ub = u52(w.z, w.w);
@@ -459,7 +474,150 @@ struct NormalStream {
     return z0;
   }
 
+  // ---- draws for discrete-event and count models (Gillespie, tau-leaping, chain-binomial).  Each consumes WHOLE blocks of the
+  // stream, like pair(): (u0, u1) below are the uniforms uniform_pair() would have returned for the same block. ----
+
+  // two Exp(1) draws from one block: e_i = -log(u_i), the log from the LDS table (neg2_log_tab, ~1.5 ulp)
+  __device__ __forceinline__ void exponential_pair(double &e0, double &e1) {
+    double u0, u1;
+    uniform_pair(u0, u1);
+    e0 = 0.5 * neg2_log_tab(u0);
+    e1 = 0.5 * neg2_log_tab(u1);
+  }
+  // one step of Gillespie's direct method from one block: the waiting time e = -log(u0) (to be divided by the total rate) and
+  // the uniform u = u1 that picks the event
+  __device__ __forceinline__ void event_pair(double &e, double &u) {
+    double u0;
+    uniform_pair(u0, u);
+    e = 0.5 * neg2_log_tab(u0);
+  }
+  // f(e, u) -> bool with the event pairs of successive blocks, in stream order, until f returns false or max_events calls are
+  // made; returns the number of calls, and the stream has advanced by exactly that many blocks.  The loop a simulator whose trip
+  // count depends on its draws should use: a lane per particle runs the re-spelled block generator with its constants loaded
+  // once; a team of 4 | 16 lanes turns a group of W blocks into (e, u) side by side, one block per lane, log included, and
+  // consumes them through DPP broadcasts with compile-time lanes, dropping the rest of the group at the first false (all
+  // lanes of a team see the same data, so the exit is uniform over the team).
+  template <class F>
+  __device__ __forceinline__ int while_events(const int max_events, F &&f) {
+    if (coop == 4) return while_events_team<4>(max_events, f);
+    if (coop == 16) return while_events_team<16>(max_events, f);
+    if (coop == 0) return while_events_lane(max_events, f);
+    int count = 0;
+    while (count < max_events) {
+      double e, u;
+      event_pair(e, u);
+      ++count;
+      if (!f(e, u)) break;
+    }
+    return count;
+  }
+  // (Both count draws take exp and log from this header -- exp_tab, log_fast: about an ulp, a few dozen instructions each.)
+  // Poisson(lambda), lambda <= 2^30.  lambda <= 0: 0, no block.  lambda < 10: sequential-search inversion of u0 of ONE block
+  // (at most 1000 steps).  Otherwise Hoermann's PTRS (transformed rejection with squeeze, Insurance: Mathematics and Economics
+  // 12, 1993), one block per trial, at most 64 trials (then floor(lambda); 1.15 - 1.33 trials per draw).
+  __device__ __forceinline__ int poisson(const double lambda) {
+    if (!(lambda > 0.0)) return 0;
+    double u, v;
+    if (lambda < 10.0) {
+      uniform_pair(u, v);
+      double p = exp_tab(-lambda), c = p;
+      int k = 0;
+      while (u >= c && k < 1000) {
+        ++k;
+        p *= lambda / (double)k;
+        c += p;
+      }
+      return k;
+    }
+    const double b = 0.931 + 2.53 * sqrt(lambda), a = -0.059 + 0.02483 * b;
+    const double inv_alpha = 1.1239 + 1.1328 / (b - 3.4), vr = 0.9277 - 3.6224 / (b - 2.0);
+    const double log_lambda = log_fast(lambda), log_inv_alpha = log_fast(inv_alpha);
+    for (int trial = 0; trial < 64; ++trial) {
+      uniform_pair(u, v);
+      const double U = u - 0.5, us = 0.5 - fabs(U);
+      const double kf = floor((2.0 * a / us + b) * U + lambda + 0.43);
+      if (us >= 0.07 && v <= vr) return (int)kf;
+      if (kf < 0.0 || (us < 0.013 && v > us)) continue;
+      if (log_fast(v) + log_inv_alpha - log_fast(a / (us * us) + b) <= -lambda + kf * log_lambda - log_factorial(kf)) return (int)kf;
+    }
+    return (int)floor(lambda);
+  }
+  // Binomial(n, p).  n <= 0 or p <= 0: 0, p >= 1: n, no block.  p > 1/2: n - binomial(n, 1 - p).  n p < 10: sequential-search
+  // inversion of u0 of ONE block.  Otherwise Hoermann's BTRS (J. Statist. Comput. Simul. 46, 1993), one block per trial, at
+  // most 64 trials (then the mode).
+  __device__ __forceinline__ int binomial(const int n, const double p) {
+    if (n <= 0 || !(p > 0.0)) return 0;
+    if (p >= 1.0) return n;
+    if (p > 0.5) return n - binomial_lower(n, 1.0 - p);
+    return binomial_lower(n, p);
+  }
+
  private:
+  __device__ __forceinline__ int binomial_lower(const int n, const double p) {      // 0 < p <= 1/2
+    const double q = 1.0 - p, r = p / q, nd = (double)n;
+    double u, v;
+    if (nd * p < 10.0) {
+      uniform_pair(u, v);
+      double pk = exp_tab(nd * log_fast(q)), c = pk;                   // (1 - p)^n, n p < 10
+      int k = 0;
+      while (u >= c && k < n && k < 1000) {                            // (n p < 10: P(k > 1000) = 0 in binary64; the bound is for a u above the rounded sum)
+        ++k;
+        pk *= r * (double)(n - k + 1) / (double)k;
+        c += pk;
+      }
+      return k;
+    }
+    const double spq = sqrt(nd * p * q), b = 1.15 + 2.53 * spq, a = -0.0873 + 0.0248 * b + 0.01 * p, c = nd * p + 0.5;
+    const double vr = 0.92 - 4.2 / b, alpha = (2.83 + 5.1 / b) * spq, m = floor((nd + 1.0) * p);
+    const double log_r = log_fast(r);
+    for (int trial = 0; trial < 64; ++trial) {
+      uniform_pair(u, v);
+      const double U = u - 0.5, us = 0.5 - fabs(U);
+      const double kf = floor((2.0 * a / us + b) * U + c);
+      if (us >= 0.07 && v <= vr) return (int)kf;
+      if (kf < 0.0 || kf > nd) continue;
+      // log f(k) / f(m) = log m! + log (n - m)! - log k! - log (n - k)! + (k - m) log r, summed in that order (most trials end at
+      // the squeeze above)
+      const double lf = log_factorial(m) + log_factorial(nd - m) - log_factorial(kf) - log_factorial(nd - kf);
+      if (log_fast(v * alpha / (a / (us * us) + b)) <= lf + (kf - m) * log_r) return (int)kf;
+    }
+    return (int)m;
+  }
+  // a lane per particle: the loop over the stream's blocks in its re-spelled form (namespace loop; same bits as event_pair)
+  template <class F>
+  __device__ __forceinline__ int while_events_lane(const int max_events, F &f) {
+    const loop::Regs c = loop::Regs::load();
+    int count = 0;
+    while (count < max_events) {
+      const u32x4 w = loop::stream_block(seed, pid, purpose, iter, k++);
+      const double e = 0.5 * loop::neg2_log_tab(loop::u52(w.x, w.y, c));
+      ++count;
+      if (!f(e, loop::u52(w.z, w.w, c))) break;
+    }
+    return count;
+  }
+  // the events of one group, lane J's after lane J - 1's, while f says go on and the bound allows
+  template <int W, class F, int... J>
+  __device__ __forceinline__ bool hand_out_events(const double ge, const double gu, const int max_events, int &count, F &f, lane_seq<J...>) {
+    bool go = true;
+    ((go = go && count < max_events && (++count, f(team_pick_ct<W, J>(ge), team_pick_ct<W, J>(gu)))), ...);
+    return go;
+  }
+  // a team per particle: blocks k + count + q on lane q, one block per lane per group
+  template <int W, class F>
+  __device__ __forceinline__ int while_events_team(const int max_events, F &f) {
+    using lanes = typename make_lane_seq<W>::type;
+    const uint32_t q = threadIdx.x & (uint32_t)(W - 1);
+    int count = 0;
+    bool go = true;
+    while (go && count < max_events) {
+      const u32x4 w = stream_block(seed, pid, purpose, iter, k + (uint32_t)count + q);
+      const double ge = 0.5 * neg2_log_tab(u52(w.x, w.y)), gu = u52(w.z, w.w);
+      go = hand_out_events<W>(ge, gu, max_events, count, f, lanes{});
+    }
+    k += (uint32_t)count;
+    return count;
+  }
   // a lane per particle, the re-spelled loop (namespace loop)
   template <class F>
   __device__ __forceinline__ void for_pairs_lane(const int n, F &f) {

@@ -49,3 +49,27 @@ def sir_gillespie(seed=11, N=100, i0=5, t_max=30.0, n_grid=16):
         return float(np.sqrt(np.mean((simulate(theta[0], theta[1]) - data) ** 2)))
 
     return simulate, f_dist
+
+
+def sir_observation(theta=(0.3, 0.1), S0=99, I0=1, R0=0, t_max=160.0, seed=123):
+    """An observation for `StochasticSIR` made the way the reference's documentation makes one (docs/src/example.md:75-148):
+    one Gillespie run at theta = (beta, gamma) with NumPy's generator, summarised as
+    dict(total_infected, peak_infected, t_peak).  (The seed decides whether the epidemic takes off at all.)"""
+    rng = np.random.default_rng(seed)
+    beta, gamma = float(theta[0]), float(theta[1])
+    N = S0 + I0 + R0
+    S, I, R, t = int(S0), int(I0), int(R0), 0.0
+    peak, t_peak = I, 0.0
+    while t < t_max and I > 0:
+        infection_rate, recovery_rate = beta * S * I / N, gamma * I
+        total_rate = infection_rate + recovery_rate
+        if not total_rate > 0.0:
+            break
+        t += rng.exponential(1.0 / total_rate)
+        if rng.random() < infection_rate / total_rate:
+            S, I = S - 1, I + 1
+        else:
+            I, R = I - 1, R + 1
+        if I > peak:
+            peak, t_peak = I, t
+    return dict(total_infected=float(R), peak_infected=float(peak), t_peak=float(t_peak))

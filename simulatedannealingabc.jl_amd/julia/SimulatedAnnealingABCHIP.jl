@@ -20,7 +20,7 @@ import Dates
 import Base: show
 
 export sabc, update_population!, RandomWalk, DifferentialEvolution, StretchMove,
-       DeviceDistance, GaussianIID, Gaussian2D, GandK, LotkaVolterra, DeviceSource, SourcePrior, comm_unique_id
+       DeviceDistance, GaussianIID, Gaussian2D, GandK, LotkaVolterra, DeviceSource, StochasticSIR, SourcePrior, comm_unique_id
 
 const libsabc = get(ENV, "SABC_HIP_LIB", joinpath(@__DIR__, "..", "libsabc_hip.so"))
 
@@ -150,6 +150,26 @@ DeviceSource(source, n_para, n_stats; params=Float64[]) = DeviceSource(source, n
 model_id(::DeviceSource) = Int32(5)
 n_stats(m::DeviceSource) = m.n_stats
 params(m::DeviceSource) = m.params
+
+"""
+    StochasticSIR(data_obs; S0=99, I0=1, R0=0, t_max=160.0, n_stats=3)
+
+The reference's documentation example (docs/src/example.md:75-198) on the device: Gillespie's direct method for θ = (β, γ),
+`data_obs = (total_infected = ..., peak_infected = ..., t_peak = ...)`; ρ = the three squared differences (`n_stats = 3`) or
+their sum (`n_stats = 1`).  A `DeviceSource` of the HIP text shipped next to the library (device_sources/sir.hip).
+"""
+function StochasticSIR(data_obs; t_max=160.0, n_stats::Integer=3, compartments...)
+    # keywords S0, I0, R0 (the reference's spelling), collected here so that the defaults sit next to their names
+    c = merge(NamedTuple{(Symbol("S0"), Symbol("I0"), Symbol("R0"))}((99, 1, 0)), values(compartments))
+    length(c) == 3 || throw(ArgumentError("unknown keyword: the compartments are S0, I0, R0"))
+    s0, i0, r0 = Int(c[1]), Int(c[2]), Int(c[3])
+    (s0 >= 0 && r0 >= 0) || throw(ArgumentError("compartments must be non-negative"))
+    i0 >= 1 || throw(ArgumentError("I0 must be at least 1"))
+    n_stats in (1, 3) || throw(ArgumentError("n_stats is 3 (one distance per statistic) or 1 (their sum)"))
+    text = read(joinpath(@__DIR__, "..", "device_sources", "sir.hip"), String)
+    obs = Float64[data_obs.total_infected, data_obs.peak_infected, data_obs.t_peak]
+    DeviceSource("#define SIR_N_STATS $(n_stats)\n" * text, 2, Int(n_stats), Float64[s0, i0, r0, t_max, obs...])
+end
 """
     SourcePrior(d)
 

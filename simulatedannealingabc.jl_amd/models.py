@@ -4,6 +4,8 @@
 Definitions (and the observed summaries each one is compared with) are in DESIGN.md."""
 from __future__ import annotations
 
+import os
+
 import numpy as np
 
 from . import _lib
@@ -142,7 +144,15 @@ class DeviceSource(DeviceDistance):
     simulation stream; `rng.for_pairs(n, [&](double z0, double z1) { ... })` hands the next n pairs to the lambda in stream
     order -- the loop to draw the bulk of a simulation with: small populations (one launch per call, a team of 4 or 16
     lanes per particle) then generate 16 or 64 pairs at a time, four blocks per lane.  The simulator must be a function of its arguments and
-    its draws alone (the lanes of a quad run it side by side).  `params` is the `params` list given here.  The source is compiled at run time (hipRTC, gfx950) into
+    its draws alone (the lanes of a quad run it side by side).
+
+    Discrete-event and count models draw whole blocks of the same stream: `rng.exponential_pair(e0, e1)` two Exp(1) draws,
+    `rng.event_pair(e, u)` the waiting time -log(u0) and the event-choice uniform u1 of one step of Gillespie's direct method,
+    `rng.poisson(lambda)` (inversion below 10, PTRS above; lambda <= 2^30) and `rng.binomial(n, p)` (inversion for n p < 10, BTRS
+    above) counts, and `rng.while_events(max_events, [&](double e, double u) { ...; return go_on; })` -- the loop whose trip
+    count depends on the draws: the lambda gets the event pairs of successive blocks until it returns false or `max_events`
+    calls are made (the bound is mandatory), the call returns their number and the stream has advanced by exactly that many
+    blocks; a team of lanes generates a group of events side by side and drops the rest at the first false.  `params` is the `params` list given here.  The source is compiled at run time (hipRTC, gfx950) into
     the same fused propose -> simulate -> ECDF -> accept kernel as the built-in simulators.  n_stats <= 64 (_lib.MAX_SOURCE_STATS;
     above 16 the wide form of the kernels).  `params` holds at most 32 values: observations the simulator compares
     against (a time series) belong in the source itself, e.g. `__constant__ double kObs[48] = {...};`."""
@@ -170,3 +180,40 @@ class DeviceSource(DeviceDistance):
         if rc:
             raise _lib.SABCError(rc, "compiling the device simulator failed:\n" + log.value.decode("utf-8", "replace"))
         return True
+
+
+_SOURCES = os.path.join(os.path.dirname(os.path.abspath(__file__)), "device_sources")
+
+
+def device_source_text(name):
+    """The text of a simulator shipped with the package as HIP source (device_sources/<name>.hip)."""
+    with open(os.path.join(_SOURCES, name + ".hip"), encoding="utf-8") as f:
+        return f.read()
+
+
+class StochasticSIR(DeviceSource):
+    """The reference's documentation example (docs/src/example.md:75-198) on the device: a stochastic SIR epidemic by
+    Gillespie's direct method, theta = (beta, gamma), started at (S0, I0, R0) and run while t < t_max and I > 0.
+    `data_obs` = (total_infected, peak_infected, t_peak) -- a sequence, or a mapping with those keys --; rho = the three squared
+    differences to it (n_stats=3, `f_dist_multi_stats`) or their sum (n_stats=1, `f_dist_single_stat`).  The model is the HIP
+    source device_sources/sir.hip, compiled like any `DeviceSource`; `examples.sir_observation` simulates an observation."""
+
+    def __init__(self, data_obs, S0=99, I0=1, R0=0, t_max=160.0, n_stats=3):
+        comp = []
+        for name, v in (("S0", S0), ("I0", I0), ("R0", R0)):
+            if isinstance(v, bool) or float(v) != int(v) or int(v) < 0:
+                raise ValueError(f"{name} must be a non-negative integer, got {v!r}")
+            comp.append(int(v))
+        if comp[1] < 1:
+            raise ValueError("I0 must be at least 1: an epidemic without an infected individual has no events")
+        if int(n_stats) not in (1, 3):
+            raise ValueError("n_stats is 3 (one distance per statistic) or 1 (their sum)")
+        if hasattr(data_obs, "keys"):
+            data_obs = [data_obs[k] for k in ("total_infected", "peak_infected", "t_peak")]
+        obs = [float(x) for x in data_obs]
+        if len(obs) != 3:
+            raise ValueError("data_obs holds (total_infected, peak_infected, t_peak)")
+        self.S0, self.I0, self.R0 = comp
+        self.t_max, self.data_obs = float(t_max), tuple(obs)
+        super().__init__(f"#define SIR_N_STATS {int(n_stats)}\n" + device_source_text("sir"), 2, int(n_stats),
+                         [*comp, self.t_max, *obs])

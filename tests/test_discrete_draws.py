@@ -1,0 +1,289 @@
+"""The draws of discrete-event and count models in the device generator (csrc/device_rng.hpp: NormalStream::exponential_pair,
+event_pair, while_events, poisson, binomial).
+
+CPU: the Python restatement of the algorithms (tests/discrete_draws_ref.py, over the oracle's Philox blocks) draws from the
+right distributions -- chi-square against scipy.stats' pmf, Kolmogorov-Smirnov of the SIR statistics against an independent
+NumPy Gillespie -- and the sources compile.  GPU: the device's draws equal the restatement's, block for block."""
+import numpy as np
+import pytest
+
+from tests.cases import SEED
+from tests.discrete_draws_ref import Stream, sir_statistics
+
+N_DRAWS = 20_000
+POISSON_CASES = [0.5, 4.0, 9.99, 10.0, 35.0, 1000.0]
+BINOMIAL_CASES = [(10, 0.3), (40, 0.5), (1000, 0.02), (1000, 0.4), (10 ** 6, 0.7), (25, 0.9)]
+
+# 16 x poisson(theta0), 16 x binomial((int)p[0], theta1), 8 x event_pair, 8 x exponential_pair: 64 values in draw order
+PROBE_SRC = r"""
+__device__ void sabc_user_simulate(const double *theta, const double *p, sabc::NormalStream &rng, double *rho) {
+  for (int j = 0; j < 16; ++j) rho[j] = (double)rng.poisson(theta[0]);
+  for (int j = 0; j < 16; ++j) rho[16 + j] = (double)rng.binomial((int)p[0], theta[1]);
+  for (int j = 0; j < 8; ++j) { double e, u; rng.event_pair(e, u); rho[32 + 2 * j] = e; rho[33 + 2 * j] = u; }
+  for (int j = 0; j < 8; ++j) { double e0, e1; rng.exponential_pair(e0, e1); rho[48 + 2 * j] = e0; rho[49 + 2 * j] = e1; }
+}
+"""
+PROBE_N = 40                      # binomial: inversion for p < 0.25, BTRS up to 0.5, both again reflected above
+
+# a loop cut short by its lambda (after `stop` events, stop = 1 + floor(theta0) in 1..40: inside the first group of a team, at
+# its end, groups later) or by its bound (p[0] = 24); the pair() drawn after it must be the one of block `count`
+CUT_SRC = r"""
+__device__ void sabc_user_simulate(const double *theta, const double *p, sabc::NormalStream &rng, double *rho) {
+  const int stop = 1 + (int)theta[0];
+  int seen = 0;
+  double acc = 0.0;
+  const int count = rng.while_events((int)p[0], [&](const double e, const double u) {
+    acc += e + u;
+    return ++seen < stop;
+  });
+  double z0, z1;
+  rng.pair(z0, z1);
+  rho[0] = (double)count;
+  rho[1] = acc;
+  rho[2] = fabs(z0);
+  rho[3] = fabs(theta[0] - p[1]) + 0.1 * fabs(z1);
+}
+"""
+CUT_BOUND = 24
+
+# Reed-Frost chain-binomial epidemic, theta = (per-contact infection probability q, reporting rate), 12 generations:
+# I_{g+1} ~ Binomial(S_g, 1 - (1 - q)^I_g); observed: Poisson(rate x total infected) and Poisson(rate x peak) against p[2], p[3]
+CHAIN_BINOMIAL_SRC = r"""
+__device__ void sabc_user_simulate(const double *theta, const double *p, sabc::NormalStream &rng, double *rho) {
+  int S = (int)p[0], I = (int)p[1], total = I, peak = I;
+  for (int g = 0; g < 12; ++g) {
+    const double p_inf = 1.0 - pow(1.0 - theta[0], (double)I);
+    const int born = rng.binomial(S, p_inf);
+    S -= born;
+    I = born;
+    total += born;
+    peak = born > peak ? born : peak;
+  }
+  rho[0] = fabs((double)rng.poisson(theta[1] * (double)total) - p[2]);
+  rho[1] = fabs((double)rng.poisson(theta[1] * (double)peak) - p[3]);
+}
+"""
+CHAIN_BINOMIAL_PARAMS = [400, 3, 90.0, 25.0]
+
+
+def chain_binomial_f(O, pid, it, theta, params=CHAIN_BINOMIAL_PARAMS):
+    rng = Stream(O, SEED, pid, it)
+    S, I = int(params[0]), int(params[1])
+    total = peak = I
+    for _ in range(12):
+        born = rng.binomial(S, 1.0 - (1.0 - theta[0]) ** I)
+        S -= born
+        I = born
+        total += born
+        peak = max(peak, born)
+    return abs(rng.poisson(theta[1] * total) - params[2]), abs(rng.poisson(theta[1] * peak) - params[3])
+
+
+def chi_square_p(draws, pmf_of, lo, hi):
+    """p-value of Pearson's chi-square of integer draws against a pmf on lo..hi, cells pooled from the left to an expectation
+    of at least 5 (the two tails beyond lo..hi go into the outer cells)."""
+    from scipy import stats
+    n = len(draws)
+    ks = np.arange(lo, hi + 1)
+    expect = n * pmf_of(ks)
+    expect[0] += n * (1.0 - pmf_of(ks).sum()) / 2.0
+    expect[-1] += n * (1.0 - pmf_of(ks).sum()) / 2.0
+    counts = np.bincount(np.clip(draws, lo, hi) - lo, minlength=len(ks)).astype(float)
+    cells_e, cells_c, e_acc, c_acc = [], [], 0.0, 0.0
+    for e, c in zip(expect, counts):
+        e_acc += e
+        c_acc += c
+        if e_acc >= 5.0:
+            cells_e.append(e_acc)
+            cells_c.append(c_acc)
+            e_acc = c_acc = 0.0
+    cells_e[-1] += e_acc                                     # what is left of the right tail joins the last cell
+    cells_c[-1] += c_acc
+    cells_e, cells_c = np.array(cells_e), np.array(cells_c)
+    assert len(cells_e) >= 3 and abs(cells_e.sum() - n) < 1e-6 * n and cells_c.sum() == n
+    chi2 = float(((cells_c - cells_e) ** 2 / cells_e).sum())
+    return float(stats.chi2.sf(chi2, len(cells_e) - 1))
+
+
+# ---------------------------------------------------------------- CPU
+@pytest.mark.parametrize("case,lam", list(enumerate(POISSON_CASES)))
+def test_poisson_draws_follow_the_pmf(O, case, lam):
+    from scipy import stats
+    rng = Stream(O, SEED + 1, 1000 + case, 3)
+    draws = np.array([rng.poisson(lam) for _ in range(N_DRAWS)])
+    dist = stats.poisson(lam)
+    lo, hi = int(dist.ppf(1e-9)), int(dist.ppf(1.0 - 1e-9))
+    p = chi_square_p(draws, dist.pmf, lo, hi)
+    print(f"poisson({lam}): chi-square p = {p:.4f}, {rng.k} blocks for {N_DRAWS} draws")
+    assert p > 1e-4
+    assert rng.k == N_DRAWS if lam < 10.0 else N_DRAWS <= rng.k <= 64 * N_DRAWS        # one block, or one per trial
+
+
+@pytest.mark.parametrize("case,n,prob", [(i, n, p) for i, (n, p) in enumerate(BINOMIAL_CASES)])
+def test_binomial_draws_follow_the_pmf(O, case, n, prob):
+    from scipy import stats
+    rng = Stream(O, SEED + 2, 2000 + case, 5)
+    draws = np.array([rng.binomial(n, prob) for _ in range(N_DRAWS)])
+    dist = stats.binom(n, prob)
+    lo, hi = int(dist.ppf(1e-9)), int(dist.ppf(1.0 - 1e-9))
+    p = chi_square_p(draws, dist.pmf, lo, hi)
+    print(f"binomial({n}, {prob}): chi-square p = {p:.4f}, {rng.k} blocks for {N_DRAWS} draws")
+    assert draws.min() >= 0 and draws.max() <= n
+    assert p > 1e-4
+    assert rng.k == N_DRAWS if n * min(prob, 1.0 - prob) < 10.0 else N_DRAWS <= rng.k <= 64 * N_DRAWS
+
+
+def test_degenerate_counts_take_no_block(O):
+    rng = Stream(O, SEED, 1, 1)
+    assert [rng.poisson(0.0), rng.poisson(-1.0), rng.binomial(0, 0.5), rng.binomial(7, 0.0), rng.binomial(7, 1.0)] == [0, 0, 0, 0, 7]
+    assert rng.k == 0
+
+
+def numpy_sir(rng, beta, gamma, S0, I0, R0, t_max):
+    """docs/src/example.md:75-148 of the reference with NumPy's generator: independent of the streams and of while_events."""
+    S, I, R, t, N = S0, I0, R0, 0.0, S0 + I0 + R0
+    times, infected = [0.0], [I0]
+    while t < t_max and I > 0:
+        infection_rate = beta * S * I / N
+        recovery_rate = gamma * I
+        total_rate = infection_rate + recovery_rate
+        t += rng.exponential(1.0 / total_rate)
+        if rng.random() < infection_rate / total_rate:
+            S, I = S - 1, I + 1
+        else:
+            I, R = I - 1, R + 1
+        times.append(t)
+        infected.append(I)
+    j = int(np.argmax(infected))
+    return float(R), float(infected[j]), times[j]
+
+
+def test_sir_statistics_follow_an_independent_gillespie(O):
+    from scipy import stats
+    runs, theta, init = 4000, (0.3, 0.1), dict(S0=99, I0=1, R0=0, t_max=160.0)
+    ours = np.array([sir_statistics(Stream(O, SEED + 3, pid, 2), *theta, **init) for pid in range(runs)])
+    rng = np.random.default_rng(99)
+    theirs = np.array([numpy_sir(rng, *theta, **init) for _ in range(runs)])
+    for j, name in enumerate(("total_infected", "peak_infected", "t_peak")):
+        p = stats.ks_2samp(ours[:, j], theirs[:, j]).pvalue
+        print(f"{name}: two-sample KS p = {p:.4f}")
+        assert p > 1e-4, name
+
+
+def test_the_observation_generator_is_the_documentation_s_model(S):
+    from sabc_amd.examples import sir_observation
+    obs = sir_observation(seed=5)
+    rng = np.random.default_rng(5)
+    want = numpy_sir(rng, 0.3, 0.1, 99, 1, 0, 160.0)
+    assert (obs["total_infected"], obs["peak_infected"], obs["t_peak"]) == want
+
+
+@pytest.mark.parametrize("n_stats", [3, 1])
+def test_the_sir_source_compiles_without_a_device(S, n_stats):
+    model = S.StochasticSIR((60.0, 20.0, 35.0), n_stats=n_stats)
+    assert model.n_para == (2,) and model.n_stats == n_stats
+    assert model.params == [99.0, 1.0, 0.0, 160.0, 60.0, 20.0, 35.0]
+    assert model.compile_check()
+
+
+def test_stochastic_sir_checks_its_compartments(S):
+    import sabc_amd
+    assert sabc_amd.StochasticSIR is S.StochasticSIR
+    obs = dict(total_infected=60, peak_infected=20, t_peak=35.0)
+    assert S.StochasticSIR(obs).params[4:] == [60.0, 20.0, 35.0]
+    for bad in (dict(S0=9.5), dict(S0=-1), dict(R0=-2), dict(I0=0), dict(I0=1.5)):
+        with pytest.raises(ValueError):
+            S.StochasticSIR(obs, **bad)
+
+
+def test_the_probe_and_chain_binomial_sources_compile_without_a_device(S):
+    assert S.DeviceSource(PROBE_SRC, 2, 64, [PROBE_N]).compile_check()
+    assert S.DeviceSource(CUT_SRC, 1, 4, [CUT_BOUND, 20.0]).compile_check()
+    assert S.DeviceSource(CHAIN_BINOMIAL_SRC, 2, 2, CHAIN_BINOMIAL_PARAMS).compile_check()
+
+
+# ---------------------------------------------------------------- GPU
+def probe_ref(O, pid, it, theta):
+    rng = Stream(O, SEED, pid, it)
+    out = [rng.poisson(theta[0]) for _ in range(16)] + [rng.binomial(PROBE_N, theta[1]) for _ in range(16)]
+    for _ in range(8):
+        out.extend(rng.event_pair())
+    for _ in range(8):
+        out.extend(rng.exponential_pair())
+    return out
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("pid0,it", [(77, 3), ((1 << 33) + 12345, 900)])
+def test_device_draws_equal_the_restatement(S, O, gpu, pid0, it):
+    """Counts exactly; the continuous draws to 1e-14: the table log is within ~1.5 ulp and libm's within 1 ulp, 2.5 ulp =
+    2.8e-16 together, and the bound is thirty times that."""
+    m = 300
+    lam = np.concatenate([[0.0, 0.05, 9.99, 10.0, 10.01], np.geomspace(0.1, 9.9, 95), np.geomspace(10.5, 3000.0, 200)])
+    prob = np.concatenate([[0.0, 1.0, 0.25, 0.5, 0.75], np.linspace(0.002, 0.998, 295)])
+    theta = np.stack([lam, np.random.default_rng(3).permutation(prob)])
+    h = S.SabcHandle(n_particles=256, model=S.DeviceSource(PROBE_SRC, 2, 64, [PROBE_N]),
+                     prior=S.product_distribution([S.Uniform(0.0, 4000.0), S.Uniform(0.0, 1.0)]), seed=SEED)
+    got = h.simulate(theta, pid0, it)
+    h.close()
+    want = np.array([probe_ref(O, pid0 + i, it, theta[:, i]) for i in range(m)]).T
+    assert got.shape == want.shape == (64, m)
+    np.testing.assert_array_equal(got[:32], want[:32])
+    assert want[:16].max() > 2500 and want[16:32].max() == PROBE_N and want[16:32].min() == 0
+    np.testing.assert_array_equal(got[33:48:2], want[33:48:2])              # event_pair's uniform is the block's second one
+    np.testing.assert_allclose(got[32:], want[32:], rtol=1e-14, atol=0.0)
+
+
+def cut_f(O, pid, it, theta, target=20.0):
+    th = float(np.atleast_1d(theta)[0])
+    rng = Stream(O, SEED, pid, it)
+    stop, seen = 1 + int(th), [0, 0.0]
+
+    def f(e, u):
+        seen[1] += e + u
+        seen[0] += 1
+        return seen[0] < stop
+    count = rng.while_events(CUT_BOUND, f)
+    assert rng.k == count == min(stop, CUT_BOUND)
+    z0, z1 = rng.normal_pair()
+    return float(count), seen[1], abs(z0), abs(th - target) + 0.1 * abs(z1)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("lanes", [0, 1, 4, 16])
+def test_while_events_leaves_the_stream_at_block_count(S, O, gpu, monkeypatch, lanes):
+    """lanes = 0: the launch chain; 1, 4, 16: one launch per call with a lane, a quad, a row of lanes per particle.  The normal
+    drawn after the loop is the one of block `count` wherever in a group of the team the lambda (or the bound) ended it."""
+    n, k = 1000, 3
+    monkeypatch.setenv("SABC_PERSISTENT", "0" if lanes == 0 else "1")
+    if lanes:
+        monkeypatch.setenv("SABC_PERSISTENT_LANES", str(lanes))
+    h = S.SabcHandle(n_particles=n, model=S.DeviceSource(CUT_SRC, 1, 4, [CUT_BOUND, 20.0]), prior=S.Uniform(0.0, 40.0), seed=SEED,
+                     algorithm=S._lib.ALG_MULTI_EPS)
+    h.initialize((k + 1) * n)
+    h.update(n_simulation=k * n, proposal=S.RandomWalk(n_para=1), resample=10 ** 9)
+    counters, (theta, _, rho), ran = dict(h.counters), h.get_population(), h.persistent_lanes
+    h.close()
+    run = cut_oracle(O, n, k)
+    assert ran == lanes
+    assert counters["n_accept"] == run.counters["n_accept"] > 0
+    np.testing.assert_array_equal(rho[0], run.rho[0])                       # the counts
+    assert set(np.unique(rho[0])) >= {1.0, 4.0, 5.0, 16.0, 17.0, float(CUT_BOUND)}
+    np.testing.assert_allclose(theta, run.theta, rtol=1e-9, atol=1e-12)
+    np.testing.assert_allclose(rho, run.rho, rtol=1e-9, atol=1e-12)
+
+
+_CUT_RUNS = {}
+
+
+def cut_oracle(O, n, k):
+    if (n, k) not in _CUT_RUNS:
+        cfg = O.make_config(n_particles=n, n_para=1, n_stats=4, model_id=O.MODEL_HOST, model_params=[], seed=SEED,
+                            prior=[(O.PRIOR_UNIFORM, 0.0, 40.0)], host_fn=O.host_simulator(lambda th, pid, it: cut_f(O, pid, it, th), 1, 4),
+                            algorithm=O.ALG_MULTI_EPS)
+        run = O.OracleRun(cfg)
+        run.initialize((k + 1) * n)
+        run.update(O.make_update_args(n_simulation=k * n, proposal=(O.PROP_RANDOMWALK, 0.8, 0.0), n_para=1, n_particles=n,
+                                      resample=10 ** 9))
+        _CUT_RUNS[(n, k)] = run
+    return _CUT_RUNS[(n, k)]
