@@ -77,8 +77,11 @@ __device__ __forceinline__ uint64_t pack64(uint32_t hi, uint32_t lo) { return ((
 // ---- f64 elementary functions specialised to the Box-Muller input ranges -------------------
 // ocml's log / sincospi / sqrt are correctly-rounded-grade general routines built on double-double
 // arithmetic (52 v_add_f64 per pair in the ISA).  The inputs here are known: u in [2^-53, 1), so
-// no special values, no denormals, no range reduction beyond one table-free step.  Each routine
-// below stays within ~1.5 ulp (tests/test_gpu_parity.py::test_normal_pairs_accuracy).
+// no special values, no denormals, no range reduction beyond one table-free step.  Worst errors against exact arithmetic, in
+// ulps of the exact result, measured and asserted by tests/test_elementary_functions.py (on the device unless marked):
+// div_fast, sqrt_fast correctly rounded at every point tested (asserted: 1 ulp); log_fast 0.73 (1); neg2_log_tab 1.87 on (0, 1),
+// 1.58 above 1 (2, restated on the CPU; the device gives the restatement's bits, as for sincos_2pi_tab and exp_tab);
+// exp_tab 1.79 (2); log_factorial 1.70 (2); absolutely, in units of 2^-53: sincos_2pi_tab 1.12 (1.25), tanh_abs_tab 2.56 (3.06).
 
 // q = a / b for finite, normal a, b of moderate magnitude: v_rcp_f64 + two Newton steps + one
 // residual correction (what the compiler emits for '/', minus the scale/fixup for special values)
@@ -171,10 +174,11 @@ __device__ __forceinline__ void rng_tables_init() {
 // with E + 1, so m / c stays in [0.707, 1.414) and there is no cancellation against E ln 2 for x near 1 (x -> 1
 // from below lands in bin 0 of E = 0: c = 1, full relative accuracy).  log(m) = logc_i + log1p(r), r = m inv_i - 1.
 // With s = -2 r (one fma against the table's -2 inv_i): -2 log1p(r) = s + s^2/4 + s^3/12 + ... + s^7/448
-// (remainder 2^-59 relative on |s| <= 2^-7).
+// (remainder 2^-59 relative on |s| <= 2^-7; half a bin is 1 << 12 of the high word -- with less added, 1 is no centre, |s|
+// reaches 1.5 x 2^-7 and bin 127's entry cancels against the polynomial just below 1: 3.9 ulp there against 1.87).
 __device__ __forceinline__ double neg2_log_tab(double x) {
   const uint32_t hi = (uint32_t)__double2hiint(x);
-  const uint32_t t = hi + 0x800u;                       // round the mantissa to 7 bits (may carry into the exponent)
+  const uint32_t t = hi + 0x1000u;                      // round the mantissa to 7 bits (may carry into the exponent)
   const uint32_t tp = t + (75u << 13);                  // ... and carry when that rounded mantissa is >= 53/128
   const int nE = 1023 - (int)(tp >> 20);                // -E
   const double m = __hiloint2double((int)(hi + ((uint32_t)nE << 20)), __double2loint(x));   // x 2^-E, exact
@@ -239,7 +243,7 @@ __device__ __forceinline__ double exp_tab(double x) {
   return ldexp(t * p, n >> 5);
 }
 
-// tanh(y) = sign(y) (1 - 2 / (exp(2|y|) + 1)): absolute error ~1e-16 (the relative error near 0 is not controlled,
+// tanh(y) = sign(y) (1 - 2 / (exp(2|y|) + 1)): absolute error 2.56 x 2^-53 = 2.8e-16 (the relative error near 0 is not controlled,
 // which is fine where it is used: inside 1 + c tanh(.))
 __device__ __forceinline__ double tanh_abs_tab(double y) {
   const double a = fmin(fabs(y), 20.0);
@@ -249,7 +253,7 @@ __device__ __forceinline__ double tanh_abs_tab(double y) {
 
 // log(k!) = lgamma(k + 1) for an integer-valued k >= 0 (the count draws' acceptance tests; the library's lgamma is a long general
 // routine): k < 16 from a table, else Stirling's series in x = k + 1 >= 17 through 1/(1188 x^9) -- the first term left out is
-// below 6e-17 absolutely, so the error is the ulp or two of (x - 1/2) log x, as for the library routine
+// below 6e-17 absolutely, so the error is that of (x - 1/2) log x: 1.70 ulp of the result at the worst (k <= 2^30)
 static __device__ const double kLogFactorial[16] = {0.0, 0.0, 0.6931471805599453, 1.791759469228055, 3.1780538303479458, 4.787491742782046, 6.579251212010101, 8.525161361065415, 10.60460290274525, 12.801827480081469, 15.104412573075516, 17.502307845873887, 19.987214495661885, 22.552163853123425, 25.19122118273868, 27.89927138384089};
 __device__ __forceinline__ double log_factorial(const double k) {
   if (k < 16.0) return kLogFactorial[(int)k];
@@ -335,7 +339,7 @@ __device__ __forceinline__ double u52(uint32_t hi, uint32_t lo, const Regs &c) {
 // (x in [2^-1000, 2^1000]: the entry's exponent must stay in range.  Box-Muller's x is in (0, 1).)
 __device__ __forceinline__ double neg2_log_tab(double x) {
   const uint32_t hi = (uint32_t)__double2hiint(x);
-  const uint32_t t = hi + 0x800u;
+  const uint32_t t = hi + 0x1000u;
   const uint32_t tp = t + (75u << 13);
   const int nE = 1023 - (int)(tp >> 20);
   const double2 e = rng_tables().logt[(t >> 13) & 127u];
@@ -477,7 +481,7 @@ struct NormalStream {
   // ---- draws for discrete-event and count models (Gillespie, tau-leaping, chain-binomial).  Each consumes WHOLE blocks of the
   // stream, like pair(): (u0, u1) below are the uniforms uniform_pair() would have returned for the same block. ----
 
-  // two Exp(1) draws from one block: e_i = -log(u_i), the log from the LDS table (neg2_log_tab, ~1.5 ulp)
+  // two Exp(1) draws from one block: e_i = -log(u_i), the log from the LDS table (neg2_log_tab, 1.87 ulp at the worst)
   __device__ __forceinline__ void exponential_pair(double &e0, double &e1) {
     double u0, u1;
     uniform_pair(u0, u1);
@@ -511,7 +515,7 @@ struct NormalStream {
     }
     return count;
   }
-  // (Both count draws take exp and log from this header -- exp_tab, log_fast: about an ulp, a few dozen instructions each.)
+  // (Both count draws take exp and log from this header -- exp_tab 1.79 ulp, log_fast 0.73 ulp, a few dozen instructions each.)
   // Poisson(lambda), lambda <= 2^30.  lambda <= 0: 0, no block.  lambda < 10: sequential-search inversion of u0 of ONE block
   // (at most 1000 steps).  Otherwise Hoermann's PTRS (transformed rejection with squeeze, Insurance: Mathematics and Economics
   // 12, 1993), one block per trial, at most 64 trials (then floor(lambda); 1.15 - 1.33 trials per draw).

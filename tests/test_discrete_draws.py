@@ -7,6 +7,7 @@ NumPy Gillespie -- and the sources compile.  GPU: the device's draws equal the r
 import numpy as np
 import pytest
 
+from tests import elementary_ref as R
 from tests.cases import SEED
 from tests.discrete_draws_ref import Stream, sir_statistics
 
@@ -203,8 +204,25 @@ def test_the_probe_and_chain_binomial_sources_compile_without_a_device(S):
 
 
 # ---------------------------------------------------------------- GPU
-def probe_ref(O, pid, it, theta):
-    rng = Stream(O, SEED, pid, it)
+class TableLogStream(Stream):
+    """The waiting times as the device computes them: half the table log of the restated u52 (tests/elementary_ref.py)."""
+
+    def uniform_pair(self):
+        w = self.O.stream_block(self.seed, self.pid, self.purpose, self.it, self.k)
+        self.k += 1
+        return R.u52(w[0], w[1]), R.u52(w[2], w[3])
+
+    def exponential_pair(self):
+        u0, u1 = self.uniform_pair()
+        return 0.5 * R.neg2_log_tab(u0), 0.5 * R.neg2_log_tab(u1)
+
+    def event_pair(self):
+        u0, u1 = self.uniform_pair()
+        return 0.5 * R.neg2_log_tab(u0), u1
+
+
+def probe_ref(O, pid, it, theta, stream=Stream):
+    rng = stream(O, SEED, pid, it)
     out = [rng.poisson(theta[0]) for _ in range(16)] + [rng.binomial(PROBE_N, theta[1]) for _ in range(16)]
     for _ in range(8):
         out.extend(rng.event_pair())
@@ -216,8 +234,9 @@ def probe_ref(O, pid, it, theta):
 @pytest.mark.gpu
 @pytest.mark.parametrize("pid0,it", [(77, 3), ((1 << 33) + 12345, 900)])
 def test_device_draws_equal_the_restatement(S, O, gpu, pid0, it):
-    """Counts exactly; the continuous draws to 1e-14: the table log is within ~1.5 ulp and libm's within 1 ulp, 2.5 ulp =
-    2.8e-16 together, and the bound is thirty times that."""
+    """Counts exactly; the continuous draws to 1e-14 of libm's: the table log is within 2 ulp (1.87 measured against exact
+    arithmetic, tests/test_elementary_functions.py) and libm's within 1 ulp, 3 ulp = 3.3e-16 together, and the bound is thirty
+    times that.  Against the table log's own restatement they are equal bit for bit."""
     m = 300
     lam = np.concatenate([[0.0, 0.05, 9.99, 10.0, 10.01], np.geomspace(0.1, 9.9, 95), np.geomspace(10.5, 3000.0, 200)])
     prob = np.concatenate([[0.0, 1.0, 0.25, 0.5, 0.75], np.linspace(0.002, 0.998, 295)])
@@ -232,6 +251,10 @@ def test_device_draws_equal_the_restatement(S, O, gpu, pid0, it):
     assert want[:16].max() > 2500 and want[16:32].max() == PROBE_N and want[16:32].min() == 0
     np.testing.assert_array_equal(got[33:48:2], want[33:48:2])              # event_pair's uniform is the block's second one
     np.testing.assert_allclose(got[32:], want[32:], rtol=1e-14, atol=0.0)
+    # ... and bit for bit what the table log's restatement gives for the same uniforms
+    table = np.array([probe_ref(O, pid0 + i, it, theta[:, i], TableLogStream) for i in range(m)]).T
+    np.testing.assert_array_equal(got[:32], table[:32])
+    np.testing.assert_array_equal(got[32:].view(np.uint64), table[32:].view(np.uint64))
 
 
 def cut_f(O, pid, it, theta, target=20.0):

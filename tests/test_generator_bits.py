@@ -12,6 +12,11 @@ every build since has to reproduce them exactly:
   chain     a 2000-particle, 40-update cfg2 run through the launch chain and through the one-launch form with 1 / 4 / 16 lanes
             per particle: final theta, u, rho, epsilon and the per-update history
 
+Re-recorded once since, on purpose: neg2_log_tab rounded its mantissa by a quarter of a bin instead of half (tests/
+test_elementary_functions.py), and the correction moves about a quarter of all table logs to another table entry.  The pairs
+whose first uniform stays in its bin kept both values bit for bit, the others moved by 2 ulp at the most (manifest.json,
+"rerecorded").
+
 Recording (on a GPU, with the build to record from):  python tests/test_generator_bits.py --record <commit>"""
 import json
 import os

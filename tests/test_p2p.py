@@ -377,6 +377,10 @@ def test_p2p_a_shard_destroyed_while_its_peer_is_inside_a_call_one_process(S, gp
             torch.cuda.set_device(0)
             model, prior = hip_model_prior(S, case)
             h = S.SabcHandle(n_particles=n, model=model, prior=prior, seed=SEED, rank=rank, world=2)
+            # shards of one device in one process: never on one hardware queue (see run_shards_in_one_process).  Without
+            # this each shard took whatever idle stream earlier handles of the process had left behind, and whether the two
+            # shared a queue -- the self-test then runs into its bound -- hung on how many handles the tests before had made
+            h.set_stream(shard_stream(rank))
             descs[rank] = h.p2p_descriptor()
             barrier.wait()
             h.p2p_set_timeout(20_000.0)

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """One-off accuracy sweep of the device Box-Muller against the oracle's glibc normals (same Philox words):
-prints the largest absolute and relative differences over m blocks.  usage: tools/check_normals.py [m]"""
+prints the largest absolute and relative differences over m blocks.  usage: tools/check_normals.py [m]
+(The standing check of the routines underneath, one by one against exact arithmetic, is tests/test_elementary_functions.py.)"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
