@@ -497,10 +497,20 @@ constexpr int kGkMaxDraws = 128;
 constexpr int kGkParticlesPerWave = SABC_GK_PW;
 
 // (1 + z^2)^k as exp(k log(1 + z^2)): the argument of the log is >= 1 and normal, so the
-// table-driven log of device_rng.hpp applies (relative error ~ k log(1+z^2) * 2e-16)
+// table-driven log of device_rng.hpp applies (relative error ~ k log(1+z^2) * 2e-16).  The power OVERFLOWS as the definition's
+// does (exp_tab_upto<710>; exp_tab itself stops at e^700 = 1e304, which made x a finite 1e304 where the model's is +-inf -- a
+// distance of 1e304 instead of 1e30 -- from k log(1 + z^2) = 700 on: k in the hundreds): x = +-inf, or NaN for B = 0 (gk_datum).
 __device__ __forceinline__ double gk_quantile(const double *th, double c, double z) {
-  const double w = exp_tab(-0.5 * th[3] * neg2_log_tab(fma(z, z, 1.0)));
+  const double w = exp_tab_upto<710>(-0.5 * th[3] * neg2_log_tab(fma(z, z, 1.0)));
   return th[0] + th[1] * (1.0 + c * tanh_abs_tab(th[2] * z / 2.0)) * w * z;
+}
+
+// A draw as the networks below sort it where they sort the data.  A NaN (0 times inf, see bitonic_step) goes in as +inf: the
+// reference's sort puts NaN last, where +inf ties with it, and both are a distance of 1e30 (finite_or_big) -- while a NaN
+// inside a network fails every compare (the selects would duplicate one value and lose another) and is dropped by v_min / v_max.
+__device__ __forceinline__ double gk_datum(const double *th, double c, double z) {
+  const double x = gk_quantile(th, c, z);
+  return x == x ? x : INFINITY;
 }
 
 // v from lane ^ DIST, DIST a compile-time power of two: DPP quad_perm for 1 and 2 (register crossbar, no
@@ -526,9 +536,6 @@ __device__ __forceinline__ double xor_lane(double v) {
   return __hiloint2double(hi, lo);
 }
 
-// One compare-exchange step of the bitonic network.  Written with a compare and selects instead of
-// fmin / fmax: the values are never NaN, and min/max would each be preceded by a canonicalising
-// v_max_f64 x, x (a third of the sort's instructions).  Equal values may be taken from either side.
 // Lane distances 16 and 32 without the LDS crossbar: v_permlane16_swap / v_permlane32_swap (new on gfx950) exchange
 // the upper half of one register with the lower half of another.  Swapping v0's upper half (odd rows) with v1's
 // lower half (even rows) leaves every lane with BOTH elements of one pair -- the lower lanes hold the v0 pair, the
@@ -569,6 +576,8 @@ constexpr uint64_t descending_lanes(int K) { return K >= 128 ? 0ull : lane_bit(i
 // One compare-exchange step of the bitonic network.  Written with a compare and selects instead of
 // fmin / fmax: the values are never NaN, and min/max would each be preceded by a canonicalising
 // v_max_f64 x, x (a third of the sort's instructions).  Equal values may be taken from either side.
+// (Never NaN: the normals are finite, and the DATA can be NaN -- B = 0 or 1 + c tanh(g z / 2) = 0 times an overflowed
+// (1 + z^2)^k, for parameters Engine::validate() accepts -- but enter the networks through gk_datum, which makes them +inf.)
 template <int K, int J>
 __device__ __forceinline__ void bitonic_step(double &v0, double &v1) {
   constexpr int kOGT = 2, kOLT = 4;                    // LLVM FCmp predicates of __builtin_amdgcn_fcmp
@@ -674,7 +683,7 @@ __device__ __forceinline__ void gk_simulate_wave_ranks(const ModelDesc &m, const
   const bool inc = gk_increasing(th, c);                // uniform over the wave
   double z0, z1;
   box_muller(stream_block(m.seed, pid, PURPOSE_SIM, iter, (uint32_t)lane), z0, z1);
-  if (!inc) { z0 = gk_quantile(th, c, z0); z1 = gk_quantile(th, c, z1); }
+  if (!inc) { z0 = gk_datum(th, c, z0); z1 = gk_datum(th, c, z1); }
   const int i0 = 2 * lane, i1 = 2 * lane + 1;
   // bitonic sorting network over the 128 values, two per lane (element index = 2*lane + slot):
   // 28 compare-exchange steps, 7 of them inside the lane, 21 with the lane at distance j/2
@@ -699,14 +708,16 @@ __device__ __forceinline__ void gk_simulate_wave_ranks_x2(const ModelDesc &m, co
   double a0, a1, b0, b1;
   box_muller(stream_block(m.seed, pidA, PURPOSE_SIM, iter, (uint32_t)lane), a0, a1);
   box_muller(stream_block(m.seed, pidB, PURPOSE_SIM, iter, (uint32_t)lane), b0, b1);
-  if (!incA) { a0 = gk_quantile(thA, c, a0); a1 = gk_quantile(thA, c, a1); }
-  if (!incB) { b0 = gk_quantile(thB, c, b0); b1 = gk_quantile(thB, c, b1); }
+  if (!incA) { a0 = gk_datum(thA, c, a0); a1 = gk_datum(thA, c, a1); }
+  if (!incB) { b0 = gk_datum(thB, c, b0); b1 = gk_datum(thB, c, b1); }
   const bool in0 = 2 * lane < n_draws, in1 = 2 * lane + 1 < n_draws;
   a0 = in0 ? a0 : INFINITY; a1 = in1 ? a1 : INFINITY;
   b0 = in0 ? b0 : INFINITY; b1 = in1 ? b1 : INFINITY;
   bool ranks_are_block_ends = true;                     // uniform: every wanted rank is a multiple of 16
 #pragma unroll
   for (int j = 0; j < S; ++j) ranks_are_block_ends = ranks_are_block_ends && (((int)m.p[2 + j]) & 15) == 0;
+  // (Not reached in the shipped build: the host sends every rank set that is all multiples of 16 to gk_simulate_rows4
+  // (kernels.hip: launch_update), so this branch runs only in a build with SABC_GK_ROWS4=0, the A/B switch.)
   if (SABC_GK_BLOCKMAX && ranks_are_block_ends) {
     static_assert(kGkMaxDraws == 128, "the final merge is the one over 128 elements");
     bitonic_sort128_x2<kGkMaxDraws / 2>(a0, a1, b0, b1);                    // runs of 64, ascending | descending
@@ -747,7 +758,7 @@ __device__ __forceinline__ void gk_simulate_wave_ranks_x2(const ModelDesc &m, co
 // sign pattern changes by the XOR of two lane bits: one v_xor_b32 on the high word per element (13 such flips in all).
 // Per 4 particles: 120 (local) + 168 (cross-lane, + 48 ds_swizzle) + 104 (flips) + 10 (block maxima) VALU instructions, i.e.
 // ~100 per particle where the network above takes ~250.  The order statistics are the same numbers: a sorting network
-// permutes, and min / max of doubles that are never NaN select.
+// permutes, and min / max of doubles that are never NaN (gk_datum) select.
 //
 // The wanted ranks have to be multiples of 16 (BASELINE config 4: 16, 48, 80, 112): after the final merge's steps at element
 // distance 64, 32, 16 every pair of lanes (2 b, 2 b + 1) holds the ranks 16 b + 1 .. 16 b + 16, whose maximum is the order
@@ -806,7 +817,7 @@ __device__ __forceinline__ void gk_simulate_rows4(const ModelDesc &m, const doub
   for (int t = 0; t < 4; ++t) box_muller(stream_block(m.seed, pid, PURPOSE_SIM, iter, (uint32_t)(4 * rl + t)), v[2 * t], v[2 * t + 1]);
   if (!inc) {
 #pragma unroll
-    for (int i = 0; i < 8; ++i) v[i] = gk_quantile(th, c, v[i]);
+    for (int i = 0; i < 8; ++i) v[i] = gk_datum(th, c, v[i]);
   }
 #pragma unroll
   for (int i = 0; i < 8; ++i) v[i] = 8 * rl + i < n_draws ? v[i] : INFINITY;

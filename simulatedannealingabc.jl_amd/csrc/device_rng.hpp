@@ -225,8 +225,13 @@ __device__ __forceinline__ void sincos_2pi_tab(double u, double &sn, double &cs)
 // 32 e + j by the add-a-big-number trick (two's complement in the sum's low word), 2^(j/32) from the table, exp(r) by
 // its Taylor polynomial of degree 6 (remainder 4e-18).  15 VALU instructions against 21 for a table-free version with a degree-13 polynomial, and 7 polynomial
 // constants instead of 13 (the g-and-k kernel, which calls it four times per draw pair, is short of scalar registers).
-__device__ __forceinline__ double exp_tab(double x) {
-  x = fmin(fmax(x, -700.0), 700.0);
+// HI = 700: the clamp of every caller but one.  HI = 710 (gk_quantile, device_models.hpp): the same steps carry on to the end
+// of the doubles -- e = 1024 is +inf out of ldexp, so exp(x) = +inf from x = 709.79 on, as the definition has it, and the
+// values below 700 are the same bits.
+template <int HI>
+__device__ __forceinline__ double exp_tab_upto(double x) {
+  static_assert(HI == 700 || HI == 710, "the reduction is exact for |32 x / ln 2| < 2^31; 2^(j/32) exp(r) >= 1 makes e = 1024 +inf");
+  x = fmin(fmax(x, -700.0), (double)HI);
   const double tm = fma(x, 0x1.71547652b82fep+5, 0x1.8p52);             // 32 / ln 2
   const double nf = tm - 0x1.8p52;
   const int n = __double2loint(tm);
@@ -242,6 +247,7 @@ __device__ __forceinline__ double exp_tab(double x) {
   p = fma(p, r, 1.0);
   return ldexp(t * p, n >> 5);
 }
+__device__ __forceinline__ double exp_tab(double x) { return exp_tab_upto<700>(x); }
 
 // tanh(y) = sign(y) (1 - 2 / (exp(2|y|) + 1)): absolute error 2.56 x 2^-53 = 2.8e-16 (the relative error near 0 is not controlled,
 // which is fine where it is used: inside 1 + c tanh(.))

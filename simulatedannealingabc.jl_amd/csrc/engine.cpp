@@ -88,8 +88,11 @@ int Engine::validate() {
       ok = d == 2 && s == 3 && cfg_.n_model_params >= 6 && p[0] >= 2 && std::fabs(p[1]) < 1.0;
       break;
     case SABC_MODEL_GK:
-      ok = d == 4 && s == 4 && cfg_.n_model_params >= 10 && p[0] >= 1 && p[0] <= 128;
-      for (int j = 0; ok && j < 4; ++j) ok = p[2 + j] >= 1 && p[2 + j] <= p[0];
+      // the draw count and the 1-based ranks are WHOLE numbers with 1 <= rank <= n_draws <= 128 (NaN fails every test): the
+      // kernels read them as (int) -- a rank is a lane index of the wave (device_models.hpp: read_lane) -- and the choice of the
+      // sorting network looks at the same integers (kernels.hip: launch_update); a fractional value is refused, not truncated
+      ok = d == 4 && s == 4 && cfg_.n_model_params >= 10 && p[0] >= 1 && p[0] <= 128 && p[0] == std::floor(p[0]);
+      for (int j = 0; ok && j < 4; ++j) ok = p[2 + j] >= 1 && p[2 + j] <= p[0] && p[2 + j] == std::floor(p[2 + j]);
       break;
     case SABC_MODEL_LV:
       ok = d == 3 && s == 4 && cfg_.n_model_params >= 9 && p[0] >= 2 && p[1] > 0;
