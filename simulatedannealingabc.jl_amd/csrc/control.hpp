@@ -1,19 +1,15 @@
 // control.hpp -- what happens to the algorithm state between two population updates
 // (SimulatedAnnealingABC.jl:334,348-354,367-372; proposals.jl:46-60), as ONE function over the
-// ControlBlock.  It is compiled as device code and run by a single lane (k_control in kernels.hip)
+// ControlBlock.  It is compiled as device code and run by a single lane (k_control in control_kernel.hpp)
 // so that the host does not have to read the sums back after every update; the CPU engine tests
 // call the very same function on the host.
 #pragma once
 #include "host_math.hpp"
 #include "sabc_types.hpp"
 
-#ifndef SABC_CTRL_MARK
-#define SABC_CTRL_MARK(i) do { } while (0)      // (timing instrumentation of an A/B build, kernels.hip)
-#endif
-
 namespace sabc {
 
-// the multi-eps schedule's epsilons, computed ahead of the step by one lane per statistic (kernels.hip: control_on_copy) from
+// the multi-eps schedule's epsilons, computed ahead of the step by one lane per statistic (control_kernel.hpp: control_on_copy) from
 // the sums the step is about to take over; the step applies them in order, exactly as it would have computed them
 struct EpsCandidates {
   double eps[kMaxStats];
@@ -44,7 +40,6 @@ SABC_HD inline ControlFirst control_step_first(ControlBlock &cb, const ControlAr
   const int d = DD > 0 ? DD : a.d, s = SS > 0 ? SS : a.s;
   if (!(a.mode & CTRL_KEEP_SUMS))
     for (int q = 0; q < n_partials(d, s); ++q) control_take_sum(cb, a, sums_in, q);
-  SABC_CTRL_MARK(9);
   const double n = a.n_global;
   const double *S = &cb.sums[1 + 2 * s], *Q = &cb.sums[1 + 2 * s + d];
 
@@ -79,7 +74,6 @@ SABC_HD inline ControlFirst control_step_first(ControlBlock &cb, const ControlAr
       if (!hostmath::cholesky(cb.sigma, d, cb.chol)) cb.error = SABC_ERR_NOT_POSDEF;   // MvNormal(...), :42
     }
   }
-  SABC_CTRL_MARK(10);
   return CONTROL_GOES_ON;
 }
 
@@ -111,7 +105,6 @@ SABC_HD inline void control_step_second(ControlBlock &cb, const ControlArgs &a, 
     }
   }
 
-  SABC_CTRL_MARK(11);
   if (a.mode & CTRL_HISTORY) {                                                       // :367-372
     if (cb.hist_rows < a.hist_capacity) {
       if (hist) {                                    // (nullptr: a workgroup of k_update_persistent that only keeps the count)
@@ -126,7 +119,6 @@ SABC_HD inline void control_step_second(ControlBlock &cb, const ControlArgs &a, 
     }
   }
 
-  SABC_CTRL_MARK(12);
   // keep the moment sums centred: the sums in hand are relative to the old pivot, so this goes last
   if (a.mode & CTRL_PIVOT)
     for (int k = 0; k < d; ++k) cb.pivot[k] += S[k] / n;

@@ -7,11 +7,6 @@
 #include "kernels.hpp"
 #include "sabc_types.hpp"
 
-// g-and-k: order statistics at multiples of 16 from block maxima instead of the last four steps of the sort (A/B switch)
-#ifndef SABC_GK_BLOCKMAX
-#define SABC_GK_BLOCKMAX 1
-#endif
-
 namespace sabc {
 
 #define SABC_LOG2PI 1.8378770664093454835606594728112
@@ -479,7 +474,7 @@ struct Sim<SABC_MODEL_GAUSS2D, D, S> {
   }
 };
 
-#if !defined(__HIPCC_RTC__)   // the wave-cooperative g-and-k simulator has its own kernel (kernels.hip); a run-time compiled
+#if !defined(__HIPCC_RTC__)   // the wave-cooperative g-and-k simulator has its own kernels (gk_kernel.hpp); a run-time compiled
                               // user simulator never needs it, and older hipRTC compilers lack some of its builtins
 // g-and-k: x = A + B (1 + c tanh(g z / 2)) (1 + z^2)^k z; rho_j = |x_(rank_j) - obs_j|.
 // Wave-cooperative: ONE WAVEFRONT PER PARTICLE.  Lane l draws Philox block l of the particle's
@@ -491,10 +486,7 @@ constexpr int kGkMaxDraws = 128;
 // particles a wave takes through its lane-parallel phases (proposal / prior gate, ECDF, accept) between the simulations,
 // which it does one particle at a time: the lane-parallel phases cost the same for 16 busy lanes as for 64.
 // Measured on cfg4 at n = 1e6 (tools/exp_ab2.sh, two runs each): 16 per wave 610 us, 32: 544 us, 64: 540 us.
-#ifndef SABC_GK_PW
-#define SABC_GK_PW 64
-#endif
-constexpr int kGkParticlesPerWave = SABC_GK_PW;
+constexpr int kGkParticlesPerWave = 64;
 
 // (1 + z^2)^k as exp(k log(1 + z^2)): the argument of the log is >= 1 and normal, so the
 // table-driven log of device_rng.hpp applies (relative error ~ k log(1+z^2) * 2e-16).  The power OVERFLOWS as the definition's
@@ -716,9 +708,10 @@ __device__ __forceinline__ void gk_simulate_wave_ranks_x2(const ModelDesc &m, co
   bool ranks_are_block_ends = true;                     // uniform: every wanted rank is a multiple of 16
 #pragma unroll
   for (int j = 0; j < S; ++j) ranks_are_block_ends = ranks_are_block_ends && (((int)m.p[2 + j]) & 15) == 0;
-  // (Not reached in the shipped build: the host sends every rank set that is all multiples of 16 to gk_simulate_rows4
-  // (kernels.hip: launch_update), so this branch runs only in a build with SABC_GK_ROWS4=0, the A/B switch.)
-  if (SABC_GK_BLOCKMAX && ranks_are_block_ends) {
+  // order statistics at multiples of 16 from block maxima instead of the last four steps of the sort.  (Not reached any
+  // more: the host sends every rank set that is all multiples of 16 to gk_simulate_rows4 (kernels.hip: launch_update).
+  // The branch stays because taking it out changes the instructions of k_update_gk<P, false>: DESIGN.md, follow-ups.)
+  if (ranks_are_block_ends) {
     static_assert(kGkMaxDraws == 128, "the final merge is the one over 128 elements");
     bitonic_sort128_x2<kGkMaxDraws / 2>(a0, a1, b0, b1);                    // runs of 64, ascending | descending
     bitonic_merge_until_x2<kGkMaxDraws, kGkMaxDraws / 2, 16>(a0, a1, b0, b1);   // element distance 64, 32, 16

@@ -416,9 +416,7 @@ __device__ __forceinline__ double team_pick(const double v, const uint32_t j) {
 
 // simulated pairs per loop trip of NormalStream::for_pairs with a lane per particle: independent Philox / Box-Muller chains for
 // the scheduler (k_update<1,1,1,0>: 92 -> 62 VGPRs, 246 -> ~240 us at n = 1e6); the draws are still handed out in stream order
-#ifndef SABC_SIM_UNROLL
-#define SABC_SIM_UNROLL 2
-#endif
+constexpr int kSimUnroll = 2;
 
 // NormalStream's coop for a lane per particle whose for_pairs stays the plain loop over pair(): the re-spelled loop holds three
 // more vector and two more scalar registers; kernels that sit on their register cap (kernels.hpp: update_loop_coop) keep this one
@@ -632,7 +630,7 @@ struct NormalStream {
   template <class F>
   __device__ __forceinline__ void for_pairs_lane(const int n, F &f) {
     const loop::Regs c = loop::Regs::load();           // once per loop, not per pair
-#pragma unroll SABC_SIM_UNROLL
+#pragma unroll kSimUnroll
     for (int i = 0; i < n; ++i) {
       double z0, z1;
       loop::box_muller(loop::stream_block(seed, pid, purpose, iter, k++), z0, z1, c);
@@ -644,7 +642,7 @@ struct NormalStream {
   __device__ __forceinline__ void for_pairs_plain(const int n, F &&f) {
     if (coop == 4) { for_pairs_team<4>(n, f); return; }
     if (coop == 16) { for_pairs_team<16>(n, f); return; }
-#pragma unroll SABC_SIM_UNROLL
+#pragma unroll kSimUnroll
     for (int i = 0; i < n; ++i) {
       double z0, z1;
       pair(z0, z1);

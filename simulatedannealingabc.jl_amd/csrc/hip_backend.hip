@@ -465,7 +465,7 @@ int HipBackend::flush_reduce() {
     std::memset(&none, 0, sizeof(none));
     none.mode = pending_guarded_ ? CTRL_GUARDED : 0;
     const P2PView pv = p2p_view();
-    HB_LAUNCH(launch_reduce_control(partials_.get(), -1, np_, sums_stage_.get(), pending_guarded_, cb_dev_.get(), none, hist_dev_.get(), mbox_dev_, stream_, &pv,
+    HB_LAUNCH(launch_reduce_control(partials_.get(), -1, np_, sums_stage_.get(), cb_dev_.get(), none, hist_dev_.get(), mbox_dev_, stream_, &pv,
                                     tag(++p2p_.xseq), /*do_control=*/false, take_silence()), "k_reduce_control (exchange)");
   }
   prof_end(SABC_KERNEL_REDUCE);
@@ -486,7 +486,7 @@ int HipBackend::control(const ControlArgs &a) {
     p2p_.pending_xchg = false;
     prof_begin(SABC_KERNEL_REDUCE);
     // several shards over the peer-to-peer slots: reduce -> exchange -> control step, ONE launch
-    HB_LAUNCH(launch_reduce_control(partials_.get(), rows, np_, sums_stage_.get(), pending_guarded_, cb_dev_.get(), a, hist_dev_.get(), mbox_dev_, stream_,
+    HB_LAUNCH(launch_reduce_control(partials_.get(), rows, np_, sums_stage_.get(), cb_dev_.get(), a, hist_dev_.get(), mbox_dev_, stream_,
                                     xchg ? &pv : nullptr, xchg ? tag(++p2p_.xseq) : 0, true, xchg ? take_silence() : 0),
               "k_reduce_control");
     prof_end(SABC_KERNEL_REDUCE);
@@ -496,7 +496,7 @@ int HipBackend::control(const ControlArgs &a) {
     p2p_.pending_xchg = false;
     if (flush_reduce()) return -1;
     prof_begin(SABC_KERNEL_REDUCE);
-    HB_LAUNCH(launch_reduce_control(partials_.get(), -1, np_, sums_stage_.get(), pending_guarded_, cb_dev_.get(), a, hist_dev_.get(), mbox_dev_, stream_, &pv,
+    HB_LAUNCH(launch_reduce_control(partials_.get(), -1, np_, sums_stage_.get(), cb_dev_.get(), a, hist_dev_.get(), mbox_dev_, stream_, &pv,
                                     tag(++p2p_.xseq), true, take_silence()), "k_reduce_control (exchange)");
     prof_end(SABC_KERNEL_REDUCE);
     return 0;

@@ -250,7 +250,7 @@ int HipBackend::p2p_selftest() {
   return 0;
 }
 
-// What the transport reads (kernels.hip: k_p2p_pattern_*): two rounds of write -> barrier -> read every shard's samples ->
+// What the transport reads (p2p_kernel.hpp: k_p2p_pattern_*): two rounds of write -> barrier -> read every shard's samples ->
 // barrier, then the parked values go back.  Works on live populations (a set-up after sabc_initialize).
 int HipBackend::selftest_patterns(const P2PView &pv) {
   const int64_t len[3] = {(int64_t)(m_.d + m_.s + 1) * sh_.cap, (int64_t)(m_.d + m_.s + 1) * sh_.cap, (int64_t)m_.s * sh_.cap};

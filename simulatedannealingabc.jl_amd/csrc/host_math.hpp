@@ -1,7 +1,7 @@
 // host_math.hpp -- the O(s) / O(d^3) scalar pieces of a population update: both epsilon schedules
 // (SimulatedAnnealingABC.jl:92-117), the covariance from fused moment sums (proposals.jl:47,59)
 // and its Cholesky factor (implicit in MvNormal(...), proposals.jl:42).  Compiled twice: as device
-// code for the single-lane control kernel (k_control in kernels.hip, so that a population update
+// code for the single-lane control kernel (k_control in control_kernel.hpp, so that a population update
 // needs no host round trip) and as plain C++ for the operator entry points and the CPU engine tests.
 #pragma once
 #if !defined(__HIPCC_RTC__)                // (hipRTC: no standard headers, the HIP runtime is pre-included)
@@ -118,7 +118,7 @@ SABC_HD inline double pow_half_int(double x, int s) {
 }
 
 // update_epsilon_multi_eps (:100-117), one statistic at a time: the s epsilons do not depend on each other, so the control
-// kernels give each its own lane (kernels.hip: control_on_copy) -- on ONE lane the schedule is s^2 divisions and square
+// kernels give each its own lane (control_kernel.hpp: control_on_copy) -- on ONE lane the schedule is s^2 divisions and square
 // roots plus s root solves per population update: 12 us at s = 3, over a millisecond at s = 48.
 SABC_HD inline double eps_multi_cn(int s) {          // (2s+2)! / ((s+1)! (s+2)!)  (:103)
   double cn = 1.0;

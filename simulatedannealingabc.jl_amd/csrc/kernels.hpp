@@ -165,9 +165,9 @@ int launch_control(ControlBlock *cb, const ControlArgs &a, double *hist, Mailbox
 // both of the above in one launch: no collective in between (pv == nullptr), or -- several shards -- with the sum over the
 // shards taken through the peer-to-peer slots inside the same launch (p2p.hpp; seq = the exchange's sequence number).
 // rows < 0: the shard's own sums are already in `stage`.  do_control = false: the global sums into `stage`, nothing else.
-int launch_reduce_control(const double *partials, int64_t rows, int np, double *stage, bool reduce_guarded,
-                          ControlBlock *cb, const ControlArgs &a, double *hist, Mailbox *mbox, hipStream_t stream,
-                          const P2PView *pv = nullptr, uint32_t seq = 0, bool do_control = true, int silent = 0);
+int launch_reduce_control(const double *partials, int64_t rows, int np, double *stage, ControlBlock *cb, const ControlArgs &a,
+                          double *hist, Mailbox *mbox, hipStream_t stream, const P2PView *pv = nullptr, uint32_t seq = 0,
+                          bool do_control = true, int silent = 0);
 // flag barrier between the shards' streams / end-of-call status exchange / a row of known values through the slots
 // (silent: test hook -- 1 = this post is skipped, 2 = it reaches this shard's own slots only)
 int launch_p2p_barrier(const P2PView &pv, uint32_t seq, ControlBlock *cb, bool guarded, int silent, hipStream_t stream);
@@ -176,7 +176,7 @@ int launch_p2p_selftest(const P2PView &pv, uint32_t seq, int np, const double *i
                         hipStream_t stream);
 // this shard leaves the group of generation `gen`: a word into every peer's slots
 int launch_p2p_leave(const P2PView &pv, uint32_t gen, hipStream_t stream);
-// self-test of what the transport reads (kernels.hip: k_p2p_pattern_*): buf / len = population buffer 0, 1, rho of this shard
+// self-test of what the transport reads (p2p_kernel.hpp: k_p2p_pattern_*): buf / len = population buffer 0, 1, rho of this shard
 // (write: mode 0 park + pattern, 1 pattern, 2 put back) or of every shard as mapped here (check: out[0] = mismatches)
 int p2p_pattern_save_words();
 int launch_p2p_pattern_write(double *const buf[3], const int64_t len[3], double *save, uint32_t gen, int round, int rank, int mode,

@@ -1,5 +1,5 @@
 // persistent_kernel.hpp -- K4 for SMALL shards: the population updates of a call in ONE launch (k_update_persistent), and the
-// few device helpers it shares with the control kernels of kernels.hip (the LDS copy of the control block, the mailbox
+// few device helpers it shares with the control kernels of control_kernel.hpp (the LDS copy of the control block, the mailbox
 // post).  Device code only; kernels.hip instantiates it for the built-in simulators, rtc.cpp compiles it with hipRTC next
 // to update_kernel.hpp for a simulator supplied as HIP source -- same kernel, same control step.
 #pragma once

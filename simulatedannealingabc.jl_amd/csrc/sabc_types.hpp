@@ -87,7 +87,7 @@ struct ControlArgs {
 // (the resample test of :340) by polling instead of draining the stream.  Two 8-byte words, each carrying the low 32 bits
 // of the step's sequence number in its upper half and written with ONE store: a reader that finds the number in both has
 // the payload -- no fence between payload and flag (a system-scope fence in the control kernel is a write-back of the L2:
-// 2.6 us of a 9.7 us launch, tools/rc_timing.py).
+// 2.6 us of a 9.7 us launch, measured with clock reads between the phases: DESIGN.md section 4).
 //   w0 = seq32 << 32 | n_accept bits 0..31
 //   w1 = seq32 << 32 | halted << 31 | (-error) << 23 | n_accept bits 32..54
 struct Mailbox {

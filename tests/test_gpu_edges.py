@@ -221,7 +221,7 @@ def test_resample_draws_at_ragged_sizes(S, O, gpu, name):
 def test_resample_with_all_but_weightless_particles(S, O, gpu, name):
     """δ = 400 in w = exp(-δ Σ u/ū) (:126-127) leaves a few percent of the particles with all of the weight: most packed lines
     then add nothing to the running sum, whole runs of them share one bucket of the guide table, and a draw's walk from
-    its guide entry falls back to bisecting the chunk (kernels.hip: packed_search).  A resample after every update."""
+    its guide entry falls back to bisecting the chunk (resample_kernel.hpp: packed_search).  A resample after every update."""
     from tests.cases import oracle_config
     n, k, delta = 20_011, 5, 400.0
     d = len(MODELS[name]["prior"])
