@@ -10,17 +10,11 @@ namespace sabc {
 // g-and-k (BASELINE config 4): the SIMULATION is wave-per-particle (128 draws sorted across the lanes); a wave owns
 // kGkParticlesPerWave consecutive particles (a block of 4 waves 4 x that), does their proposals, prior gates, ECDF
 // lookups and accept steps one particle per lane, and simulates them one after the other in between.
+// k_update_gk: every wave takes ONE group of kGkParticlesPerWave particles and the workgroup writes one partial row for all
+// of them (several groups per wave in turn lost: DESIGN.md section 3).
 // ------------------------------------------------------------------------------------------
 constexpr int kGkD = 4, kGkS = 4;
 constexpr int kGkPerBlock = (kBlock / 64) * kGkParticlesPerWave;
-// k_update_gk: every wave takes ONE group of kGkParticlesPerWave particles and the workgroup writes one partial row for all
-// of them.  A wave taking several groups in turn was measured at n = 1e6 with groups of 16 (tools/exp_ab2.sh, three runs
-// each): 1 group 663 us, 2 groups 786 us, 4 groups 812 us -- the loop around the phases cost the register allocator 240 more
-// bytes of scratch and 16 more SGPR reloads per particle.  So: one group, and the group itself grew to 64
-// (device_models.hpp) -- the lane-parallel phases then run with all lanes busy instead of being repeated.
-// The loop itself stays in the source, over kGkReps = 1 groups: written as a plain `if (t0 < act_n)` the six kernels compile
-// to other code (102 instead of 116 VGPRs, a tenth fewer instructions), which nobody has measured yet (follow-ups).
-constexpr int kGkReps = 1;
 
 // per-wave staging of what phase 1 (propose + simulate) hands to phase 2 (ECDF) and 3 (accept)
 struct GkStage {
@@ -32,13 +26,13 @@ struct GkStage {
 };
 
 // 4 workgroups per CU (<= 128 VGPRs, 68 B of scratch outside the sort): 850 -> 755 us at n = 1e6 against 3 per CU (144 VGPRs,
-// no scratch) -- the sort waits on lane exchanges, so the extra wave pays; 5 per CU spills inside the loop (1030 us)
+// no scratch) -- the sort waits on lane exchanges, so the extra wave pays; 5 per CU spills inside the loop (1030 us).
+// (The figures of the kernel as it was then; as it stands: 102 VGPRs with ROWS4, 105 without, no scratch -- DESIGN.md.)
 // ROWS4: every wanted rank is a multiple of 16 (the host looks: launch_update) -- the simulations run four particles at a time
 // on the network of gk_simulate_rows4 only; the two-values-per-lane network stays out of this instantiation (and its
-// registers with it: kGkRows4Waves workgroups per CU)
-constexpr int kGkRows4Waves = 4;
+// registers with it)
 template <int PROP, bool ROWS4>
-__global__ void __launch_bounds__(kBlock, ROWS4 ? kGkRows4Waves : 4)
+__global__ void __launch_bounds__(kBlock, 4)
 k_update_gk(const ModelDesc m, const StepArgs c, const ControlBlock *__restrict__ cb, const PopPtrs pp, const CdfPtrs cdf,
             const PartnerView pv, const int64_t act_lo, const int64_t act_n, double *__restrict__ partials) {
   constexpr int D = kGkD, S = kGkS, NP = n_partials(D, S), PW = kGkParticlesPerWave;
@@ -50,9 +44,8 @@ k_update_gk(const ModelDesc m, const StepArgs c, const ControlBlock *__restrict_
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   GkStage &st = stage[wave];
   if (lane < NP) red[wave][lane] = 0.0;
-  for (int rep = 0; rep < kGkReps; ++rep) {
-    const int64_t t0 = (int64_t)blockIdx.x * (kGkPerBlock * kGkReps) + (wave * kGkReps + rep) * PW;
-    if (t0 >= act_n) break;                // uniform over the wave; a wave without particles goes straight to the block's sum
+  const int64_t t0 = (int64_t)blockIdx.x * kGkPerBlock + wave * PW;
+  if (t0 < act_n) {                        // uniform over the wave; a wave without particles goes straight to the block's sum
     // the wave owns particles t0 .. t0+PW-1; in the scalar phases (1a, 3) lane i < PW handles particle t0+i
     const int64_t t_mine = t0 + lane;
     const bool mine = lane < PW && t_mine < act_n;
@@ -60,56 +53,14 @@ k_update_gk(const ModelDesc m, const StepArgs c, const ControlBlock *__restrict_
     const uint64_t gid = (uint64_t)(pp.gid0 + li);
 
     // ---- phase 1a, lane-parallel over the wave's particles: proposal (:311) and prior gate (:314)
+    // -- the narrow form's draft without its simulation, the very code k_update runs (update_kernel.hpp: kDraftOnly)
     if (mine) {
-      double th[D], thp[D];
+      ParticleDraft<D, 1> q;               // (q.th, q.u, q.rp: unused)
+      update_particle_draft<kDraftOnly, D, 1, PROP, false, 1>(m, c.iter, c.prop_p0, c.prop_p1, cb, pp, pv, li, gid, q);
 #pragma unroll
-      for (int k = 0; k < D; ++k) th[k] = pp.pop[(int64_t)k * pp.cap + li];
-      double logf = 0.0;
-      if (PROP == SABC_PROP_RANDOMWALK) {
-        NormalStream ns(m.seed, gid, PURPOSE_PROP, c.iter);
-        double z[D];
-#pragma unroll
-        for (int k = 0; k < D; ++k) z[k] = ns.next();
-#pragma unroll
-        for (int k = 0; k < D; ++k) {
-          double a = 0.0;
-#pragma unroll
-          for (int l = 0; l <= k; ++l) a += cb->chol[k * D + l] * z[l];
-          thp[k] = th[k] + a;
-        }
-      } else if (PROP == SABC_PROP_DIFFEVO) {
-        uint64_t i1 = 0, i2 = 0;
-        for (uint32_t a = 0;; ++a) {
-          const u32x4 w = stream_block(m.seed, gid, PURPOSE_PROP, c.iter, a);
-          i1 = mulhi64(pack64(w.x, w.y), (uint64_t)pv.m_total);
-          i2 = mulhi64(pack64(w.z, w.w), (uint64_t)pv.m_total);
-          if (i1 != i2 || a > 64u) break;
-        }
-        double z0, z1;
-        box_muller(stream_block(m.seed, gid, PURPOSE_PROP2, c.iter, 0), z0, z1);
-        const double gamma = c.prop_p0 * (1.0 + c.prop_p1 * z0);
-        const double *p1 = partner_ptr(pv, i1), *p2 = partner_ptr(pv, i2);
-#pragma unroll
-        for (int k = 0; k < D; ++k) thp[k] = th[k] + gamma * (p1[(int64_t)k * pv.cap] - p2[(int64_t)k * pv.cap]);
-      } else {
-        const u32x4 w = stream_block(m.seed, gid, PURPOSE_PROP, c.iter, 0);
-        const uint64_t ip = mulhi64(pack64(w.x, w.y), (uint64_t)pv.m_total);
-        const double U = u52(w.z, w.w);
-        const double a = c.prop_p0;
-        const double tt = (a - 1.0) * U + 1.0;
-        const double z = tt * tt / a;
-        const double *p = partner_ptr(pv, ip);
-#pragma unroll
-        for (int k = 0; k < D; ++k) {
-          const double pk = p[(int64_t)k * pv.cap];
-          thp[k] = pk + z * (th[k] - pk);
-        }
-        logf = log(z) * (double)(D - 1);
-      }
-#pragma unroll
-      for (int k = 0; k < D; ++k) st.thp[lane][k] = thp[k];
-      st.lpp[lane] = prior_logpdf<D>(m, thp);
-      st.logf[lane] = logf;
+      for (int k = 0; k < D; ++k) st.thp[lane][k] = q.thp[k];
+      st.lpp[lane] = q.lpp;
+      st.logf[lane] = q.logf;
     }
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
@@ -230,7 +181,7 @@ k_update_gk(const ModelDesc m, const StepArgs c, const ControlBlock *__restrict_
       }
       moment_terms<D, S>(cb->pivot, accepted, th, u, drho, term);
     }
-    // sum the moment terms over the wave's PW particle lanes (lanes >= PW hold zeros) into the wave's running row, ...
+    // sum the moment terms over the wave's PW particle lanes (lanes >= PW hold zeros) into the wave's row, ...
 #pragma unroll
     for (int q = 0; q < NP; ++q) {
       double v = term[q];
@@ -238,8 +189,6 @@ k_update_gk(const ModelDesc m, const StepArgs c, const ControlBlock *__restrict_
       for (int off = PW / 2; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
       if (lane == 0) red[wave][q] += v;
     }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();         // the staging arrays are reused by the next group
   }
   // ... then over the 4 waves
   __syncthreads();

@@ -410,6 +410,7 @@ constexpr int wide_row() { return S | 1; }
 
 // the narrow form's draft without its simulation: update_particle_draft<kDraftOnly, D, 1, ..> loads theta, proposes and gates
 // with the very code k_update runs; the wide kernel simulates into its LDS row
+// (two users: k_update_wide below, and phase 1a of k_update_gk, whose waves simulate together -- gk_kernel.hpp)
 constexpr int kDraftOnly = -1;
 template <int D, int S>
 struct Sim<kDraftOnly, D, S> {
