@@ -219,10 +219,29 @@ SABC_API int64_t     sabc_host_callback_calls(const sabc_handle *h);
        __device__ void   sabc_user_prior_sample(const double *params, sabc::NormalStream &rng, double *theta_out);
        __device__ double sabc_user_prior_logpdf(const double *theta, const double *params);   // -INFINITY outside the support
    (`rng`: the particle's prior stream.)
+   OBSERVED DATA (the reference hands them to f_dist as args... / kwargs..., SimulatedAnnealingABC.jl:164,175,315) live in HBM,
+   set with sabc_set_device_data below, and are read by every function of the source -- the simulator and the prior -- through
+       int           sabc::data_segments();                   0 while nothing is set
+       long long     sabc::data_len(int segment = 0);
+       const double *sabc::data(int segment = 0);             nullptr while nothing is set
+       double        sabc::data_at(long long i, int segment = 0);
+   data_at reads through the constant address space: an index that is the same in every lane of a wave costs one scalar load
+   per wave, an index that differs per lane a vector load.  Indices are not checked.  A new data set needs no new source and
+   no new compilation.
    It is compiled with hipRTC for gfx950 against csrc/update_kernel.hpp -- the same propose -> simulate -> ECDF -> accept
    kernel, reductions and Philox streams as the built-in simulators -- and must be registered before sabc_initialize.
    On failure sabc_last_error(h) holds the compiler log. */
 SABC_API int         sabc_register_device_simulator(sabc_handle *h, const char *hip_source);
+/* SABC_MODEL_USER only: the observed data the source reads through sabc::data*().  `values`: n doubles, copied into device
+   memory the handle owns; segment_len[0 .. n_segments) sums to n, n_segments <= SABC_MAX_DATA_SEGMENTS; n = 0 drops the data.
+   Legal before or after sabc_register_device_simulator (registering again keeps the data) and between any two calls on an
+   idle handle -- the second call of the reference's getting-started example, update_population! with another y_obs.  The
+   handle's stream is synchronised first.  SABC_ERR_BAD_CONFIG (not SABC_MODEL_USER, n < 0, segment lengths negative or not
+   summing to n, too many segments) and SABC_ERR_HIP (the allocation failed) leave the old data in place. */
+#define SABC_MAX_DATA_SEGMENTS 8
+SABC_API int         sabc_set_device_data(sabc_handle *h, const double *values, int64_t n, const int64_t *segment_len,
+                                          int32_t n_segments);
+SABC_API int64_t     sabc_device_data_len(const sabc_handle *h);
 /* the compiler stage alone (needs hipRTC but no device): 0 if `hip_source` compiles into the update kernels for (d, s);
    the compiler log is copied into log_out (may be NULL) */
 SABC_API int         sabc_op_compile_device_simulator(const char *hip_source, int32_t d, int32_t s, char *log_out,

@@ -12,7 +12,8 @@ from .distributions import (Beta, Exponential, Gamma, HostPrior, LogNormal, MvNo
                             TruncatedNormal, Uniform, from_scipy, product_distribution, truncated)
 from .handle import (SabcHandle, op_build_cdf, op_cdf_eval, op_eps_multi, op_eps_single,  # noqa: F401
                      op_normal_pairs, op_philox, op_rng_peak, op_sort)
-from .models import DeviceDistance, DeviceSource, GandK, Gaussian2D, GaussianIID, HostDistance, LotkaVolterra, StochasticSIR  # noqa: F401
+from .models import (DeviceDistance, DeviceSource, GandK, Gaussian2D, GaussianIID, HostDistance, LotkaVolterra, NormalMoments,  # noqa: F401
+                     StochasticSIR, StochasticSIRSeries)
 from .proposals import DifferentialEvolution, Proposal, RandomWalk, StretchMove  # noqa: F401
 
 __all__ = [
@@ -20,6 +21,7 @@ __all__ = [
     "RandomWalk", "DifferentialEvolution", "StretchMove", "Proposal",
     "Normal", "Uniform", "Exponential", "LogNormal", "Gamma", "Beta", "TruncatedNormal", "truncated", "MvNormal", "HostPrior", "SourcePrior", "from_scipy", "Product", "product_distribution",
     "DeviceDistance", "DeviceSource", "HostDistance", "GaussianIID", "Gaussian2D", "GandK", "LotkaVolterra", "StochasticSIR",
+    "NormalMoments", "StochasticSIRSeries",
     "SabcHandle", "op_build_cdf", "op_cdf_eval", "op_eps_single", "op_eps_multi", "op_philox", "op_normal_pairs", "op_rng_peak", "op_sort",
     "build", "lib", "is_logging",
 ]

@@ -181,6 +181,17 @@ def as_host_distance(f_dist, prior, args=(), kwargs=None):
     return hd
 
 
+def _device_data(f_dist, args, kwargs):
+    """The extra args / kwargs of a call as the data segments of a device-coded simulator (the reference forwards them to
+    f_dist, :164,175,315): a DeviceSource constructed with `data_names` takes them, every other DeviceDistance refuses them."""
+    if not args and not kwargs:
+        return None
+    bind = getattr(f_dist, "bind_data", None)
+    if bind is None:
+        raise TypeError("a DeviceDistance takes its data at construction; extra args/kwargs are not forwarded")
+    return bind(args, kwargs)
+
+
 def progress_stops(n_pop, show_checkpoint, show_progressbar):
     """Progress output needs the device loop to come up for air: `update_population!` is cut into several sabc_update calls.
     Returns the update counts after which a call ends: every multiple of `show_checkpoint` (:359), every step of the
@@ -228,8 +239,9 @@ def initialization(f_dist, prior, *args, n_particles, n_simulation, v=1.0, δ=0.
             raise TypeError("f_dist must be a DeviceDistance or a callable f_dist(θ, *args, **kwargs)")
         f_dist = as_host_distance(f_dist, prior, args, kwargs)               # :163-165 shape probe
         args, kwargs = (), {}
-    if args or kwargs:
-        raise TypeError("a DeviceDistance takes its data at construction; extra args/kwargs are not forwarded")
+    data = _device_data(f_dist, args, kwargs)
+    if data is None and getattr(f_dist, "data_names", None) and getattr(f_dist, "data", None) is None:
+        raise TypeError(f"{type(f_dist).__name__} has no data: give them at construction or to this call, data_names = {f_dist.data_names!r}")
     if len(prior) not in f_dist.n_para:
         raise ValueError(f"{type(f_dist).__name__} needs a prior with {f_dist.n_para} parameters, got {len(prior)}")
     log.info("Initialization for '%s'", alg)                                  # :158
@@ -253,6 +265,8 @@ def initialization(f_dist, prior, *args, n_particles, n_simulation, v=1.0, δ=0.
     if dist is not None:
         from .dist import install_collectives
         install_collectives(h, device)
+    if data is not None:
+        h.set_data(data)                                  # y_obs of this call, in place of what the model was constructed with
     h.initialize(n_simulation)
     state = SABCstate()
     state.algorithm = alg
@@ -277,8 +291,7 @@ def update_population_(population_state: SABCresult, f_dist, prior, *args, n_sim
             raise ValueError("f_dist differs from the one this SABCresult was initialised with")
         res._model.args, res._model.kwargs = tuple(args), dict(kwargs)      # forwarded to f_dist, like :315
         f_dist, args, kwargs = res._model, (), {}
-    if args or kwargs:
-        raise TypeError("a DeviceDistance takes its data at construction; extra args/kwargs are not forwarded")
+    data = _device_data(f_dist, args, kwargs)
     if getattr(res._prior, "host_prior", False):
         # a host-callback prior is code, not data: it has to be the object (or the scipy distribution) of the initialisation
         if prior is not res._prior and prior is not getattr(res._prior, "source", None):
@@ -292,6 +305,8 @@ def update_population_(population_state: SABCresult, f_dist, prior, *args, n_sim
                 not np.array_equal(np.asarray(getattr(prior, "chol", 0.0)), np.asarray(getattr(res._prior, "chol", 0.0))):
             raise ValueError("f_dist / prior differ from the ones this SABCresult was initialised with")
     h = res._handle
+    if data is not None:
+        h.set_data(data)                                  # forwarded to f_dist, like :315: data not given leave the handle's
     if proposal is None:
         proposal = DifferentialEvolution(n_para=len(prior))                           # :254
     if not isinstance(proposal, Proposal):
@@ -366,6 +381,11 @@ def load_result(path, f_dist, prior, device=0) -> SABCresult:
     prior = as_prior(prior, int(z["seed"]) % (1 << 62))
     if not isinstance(f_dist, DeviceDistance) and callable(f_dist):
         f_dist = as_host_distance(f_dist, prior)
+    if getattr(f_dist, "data_names", None) and getattr(f_dist, "data", None) is None:
+        # (update_population_(res, model, prior, y_obs=B) sets B on the handle, not on the model: a result stored after it is
+        # loaded with a model constructed on B)
+        raise TypeError(f"{type(f_dist).__name__} has no data: a result is loaded with a model constructed on its data, "
+                        f"data_names = {f_dist.data_names!r}")
     h = SabcHandle(n_particles=n, model=f_dist, prior=prior, algorithm=_ALGORITHMS[alg], seed=int(z["seed"]), device=device)
     pop = z["population"]
     th = pop.reshape(1, -1) if prior.univariate else np.ascontiguousarray(pop.T)

@@ -297,6 +297,14 @@ int sabc_register_device_simulator(sabc_handle *h, const char *hip_source) {
   return h->be->register_device_simulator(hip_source) ? hfail(h, SABC_ERR_BAD_CONFIG) : 0;
 }
 
+int sabc_set_device_data(sabc_handle *h, const double *values, int64_t n, const int64_t *segment_len, int32_t n_segments) {
+  if (!h) return SABC_ERR_STATE;
+  h->err.clear();
+  const int rc = h->be->set_device_data(values, n, segment_len, n_segments);
+  return rc ? hfail(h, rc) : 0;
+}
+int64_t sabc_device_data_len(const sabc_handle *h) { return h ? h->be->device_data_len() : 0; }
+
 int sabc_set_host_simulator(sabc_handle *h, sabc_simulate_fn fn, void *ctx) {
   if (!h || !fn) return hset(h, SABC_ERR_BAD_CONFIG, "null host simulator");
   if (h->eng->model().model_id != SABC_MODEL_HOST) return hset(h, SABC_ERR_BAD_CONFIG, "the handle was not created with SABC_MODEL_HOST");

@@ -311,7 +311,51 @@ int HipBackend::register_device_simulator(const char *hip_source) {
       return -1;
     }
   }
+  return push_data_desc();                                // a new module starts with an empty descriptor: the data are kept
+}
+
+static_assert(SABC_MAX_DATA_SEGMENTS == 8, "RtcDataDesc and the preamble of rtc.cpp hold 8 segments");
+
+int HipBackend::push_data_desc() {
+  if (!rtc()) return 0;                                   // no module yet: register_device_simulator writes it after the load
+  hipDeviceptr_t sym = nullptr;
+  size_t bytes = 0;
+  HB_CHECK(hipModuleGetGlobal(&sym, &bytes, rtc_.module, rtc_data_symbol()), "hipModuleGetGlobal(sabc_data_desc)");
+  if (bytes != sizeof(RtcDataDesc)) { err_ = "sabc_data_desc of the compiled simulator has another layout than this library's"; return -1; }
+  HB_CHECK(hipMemcpyAsync(sym, &data_desc_, sizeof(RtcDataDesc), hipMemcpyHostToDevice, stream_), "hipMemcpy(sabc_data_desc)");
+  HB_CHECK(hipStreamSynchronize(stream_), "hipStreamSynchronize");
   return 0;
+}
+
+int HipBackend::set_device_data(const double *values, int64_t n, const int64_t *segment_len, int32_t n_segments) {
+  if (m_.model_id != SABC_MODEL_USER) { err_ = "observed data are read by a simulator from source: the handle was not created with SABC_MODEL_USER"; return SABC_ERR_BAD_CONFIG; }
+  if (n < 0 || n_segments < 0 || n_segments > SABC_MAX_DATA_SEGMENTS) { err_ = "sabc_set_device_data: n >= 0 and at most 8 segments"; return SABC_ERR_BAD_CONFIG; }
+  if (n > 0 && (!values || !segment_len)) { err_ = "sabc_set_device_data: null argument"; return SABC_ERR_BAD_CONFIG; }
+  RtcDataDesc desc;
+  int64_t sum = 0;
+  for (int k = 0; k < n_segments && n > 0; ++k) {
+    if (segment_len[k] < 0 || segment_len[k] > n) { err_ = "sabc_set_device_data: a segment length is negative or larger than n"; return SABC_ERR_BAD_CONFIG; }
+    desc.off[k] = sum;
+    desc.len[k] = segment_len[k];
+    sum += segment_len[k];
+  }
+  if (sum != n) { err_ = "sabc_set_device_data: the segment lengths do not sum to n"; return SABC_ERR_BAD_CONFIG; }
+  if (check(hipSetDevice(device_), "hipSetDevice")) return SABC_ERR_HIP;
+  // the host queues updates ahead: nothing of this handle may still be reading the old data or the old descriptor
+  if (stream_ && check(hipStreamSynchronize(stream_), "hipStreamSynchronize")) return SABC_ERR_HIP;
+  const size_t bytes = (size_t)n * sizeof(double);
+  if ((size_t)n != data_.count()) {
+    DeviceBuffer<double> fresh;
+    if (n > 0 && check(fresh.alloc((size_t)n), "hipMalloc(observed data)")) return SABC_ERR_HIP;
+    if (n > 0 && check(hipMemcpy(fresh.get(), values, bytes, hipMemcpyHostToDevice), "hipMemcpy(observed data)")) return SABC_ERR_HIP;
+    data_ = std::move(fresh);                             // (the handle is idle: the old allocation is freed here)
+  } else if (n > 0) {                                     // the same length again: the allocation is reused
+    if (check(hipMemcpy(data_.get(), values, bytes, hipMemcpyHostToDevice), "hipMemcpy(observed data)")) return SABC_ERR_HIP;
+  }
+  desc.base = data_.get();
+  desc.n_segments = n > 0 ? n_segments : 0;
+  data_desc_ = desc;
+  return push_data_desc() ? SABC_ERR_HIP : 0;
 }
 
 int HipBackend::prior_simulate() {

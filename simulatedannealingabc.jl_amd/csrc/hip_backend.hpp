@@ -34,6 +34,10 @@ class HipBackend : public Backend {
   }
   // SABC_MODEL_USER: compile the simulator source into the update kernels (rtc.hpp); the compiler log goes to error()
   int register_device_simulator(const char *hip_source);
+  // SABC_MODEL_USER: the observed data the source reads through sabc::data*() (rtc.hpp: RtcDataDesc).  0, or the SABC_ERR_*
+  // code with the text in error(); on an error the old data stay in place
+  int set_device_data(const double *values, int64_t n, const int64_t *segment_len, int32_t n_segments);
+  int64_t device_data_len() const { return (int64_t)data_.count(); }
   int host_prior_simulate() override;
   int host_update_range(const StepArgs &c, const PartnerView &pv, int64_t lo, int64_t cnt) override;
   int host_stats(int64_t *rows_out) override;
@@ -138,6 +142,9 @@ class HipBackend : public Backend {
   DeviceBuffer<double> pop_[2];
   int cur_ = 0;
   DeviceBuffer<double> rho_, knots_, coarse_, mid_;
+  DeviceBuffer<double> data_;                             // observed data of a simulator from source (set_device_data)
+  RtcDataDesc data_desc_;                                 // ... and what the loaded module's sabc_data_desc holds about them
+  int push_data_desc();                                   // writes data_desc_ into the module, if one is loaded
   int64_t mid_stride_ = 0;
   int32_t cdf_shift_[kMaxStats] = {0};
   int build_coarse(int stat);

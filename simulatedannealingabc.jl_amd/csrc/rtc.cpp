@@ -178,7 +178,41 @@ void disk_cache_store(const std::string &path, int n_kernels, const CachedModule
   if (!ok) (void)std::remove(t.c_str());
 }
 
+// ---- observed data (sabc_set_device_data): what every source-compiled unit sees ahead of the user's text ----
+// The carrier is ONE module-scope __constant__ variable, sabc_data_desc (struct RtcDataDesc of rtc.hpp): base pointer, segment
+// count, offsets and lengths.  HipBackend writes it through hipModuleGetGlobal after each module load and after each
+// sabc_set_device_data; every handle loads a module of its own, so every handle has a descriptor of its own.  No kernel
+// signature changes, and all sixteen kernels of the unit -- and the user's prior functions -- read it.
+// This text is part of the cache key below (in memory and, through it, on disk): a code object compiled before the symbols
+// existed, or with another layout of the descriptor, is never loaded in place of this one.
+const char kDataPreamble[] = R"SABC(
+struct SabcDataDesc {
+  const double *base;
+  int n_segments, reserved;
+  long long off[8], len[8];
+};
+extern "C" { __constant__ SabcDataDesc sabc_data_desc = {}; }
+namespace sabc {
+__device__ __forceinline__ int data_segments() { return sabc_data_desc.n_segments; }
+__device__ __forceinline__ long long data_len(int segment = 0) { return sabc_data_desc.len[segment]; }
+__device__ __forceinline__ const double *data(int segment = 0) {
+  return sabc_data_desc.base ? sabc_data_desc.base + sabc_data_desc.off[segment] : nullptr;
+}
+// The read goes through the constant address space.  The data are immutable during a launch: they are replaced only on an
+// idle handle (sabc_set_device_data synchronises the stream first), so no kernel runs while they change.  A later launch may
+// find the new values at the old address (a set of the same length reuses the allocation): what keeps the scalar cache from
+// serving the old ones there is the cache invalidation every kernel dispatch begins with (its acquire), not the host's
+// synchronise.  An index that is uniform in the wave becomes a scalar load (one per wave), a divergent one a global vector load.
+__device__ __forceinline__ double data_at(long long i, int segment = 0) {
+  typedef const double __attribute__((address_space(4))) *const_ptr;
+  return ((const_ptr)(sabc_data_desc.base + sabc_data_desc.off[segment]))[i];
+}
+}  // namespace sabc
+)SABC";
+
 }  // namespace
+
+const char *rtc_data_symbol() { return "sabc_data_desc"; }
 
 std::string rtc_default_csrc_dir() {
   Dl_info info;
@@ -223,7 +257,7 @@ int rtc_compile(const char *user_source, int d, int s, const std::string &csrc_d
                 "  }\n"
                 "};\n"
                 "}  // namespace sabc\n");
-  std::string src = std::string("#include \"update_kernel.hpp\"\n") + (with_persistent ? "#include \"persistent_kernel.hpp\"\n" : "") + "#line 1 \"f_dist.hip\"\n";
+  std::string src = std::string("#include \"update_kernel.hpp\"\n") + (with_persistent ? "#include \"persistent_kernel.hpp\"\n" : "") + kDataPreamble + "#line 1 \"f_dist.hip\"\n";
   src += user_source;
   src += tail;
 
@@ -249,7 +283,7 @@ int rtc_compile(const char *user_source, int d, int s, const std::string &csrc_d
 #undef SABC_RTC_STR
 #undef SABC_RTC_STR2
   const std::string cache_key = std::to_string(d) + "," + std::to_string(s) + (user_prior ? ",P" : "") + (with_persistent ? ",1L4L16" : "") + "," + extra + "," +
-                                geometry + "\n" + user_source;
+                                geometry + "\n" + kDataPreamble + "\n" + user_source;
   if (out) {
     std::lock_guard<std::mutex> lock(g_cache_mutex);
     auto hit = g_cache.find(cache_key);

@@ -2,6 +2,7 @@
 // fused update kernel the built-in simulators use (update_kernel.hpp), loaded as a code-object module.
 #pragma once
 #include <hip/hip_runtime_api.h>
+#include <cstdint>
 #include <string>
 
 namespace sabc {
@@ -32,6 +33,15 @@ int rtc_build(const char *user_source, int d, int s, const std::string &csrc_dir
 int rtc_compile(const char *user_source, int d, int s, const std::string &csrc_dir, RtcKernels *out, std::string *log,
                 size_t *code_size, bool user_prior = false, bool with_persistent = false);
 void rtc_release(RtcKernels *k);
+// Observed data (sabc_set_device_data): every source-compiled unit defines one module-scope __constant__ variable of this
+// layout ahead of the user's text (rtc.cpp: kDataPreamble, which declares the same struct to the device compiler); the
+// backend writes it through hipModuleGetGlobal(rtc_data_symbol()).
+struct RtcDataDesc {
+  const double *base = nullptr;
+  int32_t n_segments = 0, reserved = 0;
+  long long off[8] = {0}, len[8] = {0};
+};
+const char *rtc_data_symbol();
 // directory of this shared library + "/csrc" (the headers ship next to the library)
 std::string rtc_default_csrc_dir();
 

@@ -51,6 +51,34 @@ def sir_gillespie(seed=11, N=100, i0=5, t_max=30.0, n_grid=16):
     return simulate, f_dist
 
 
+def sir_series_observation(theta=(0.3, 0.1), t_obs=None, S0=99, I0=1, R0=0, t_max=160.0, seed=123):
+    """An observation for `StochasticSIRSeries`: one Gillespie run at theta = (beta, gamma) with NumPy's generator, observed at
+    the increasing times `t_obs` (default: 0, 5, ..., 155) the way device_sources/sir_series.hip observes a simulation -- I(t_k)
+    is the number infected just before the first event later than t_k, the final number once no event follows.
+    Returns (t_obs, I_obs) as float64 arrays."""
+    rng = np.random.default_rng(seed)
+    t_obs = np.arange(0.0, 160.0, 5.0) if t_obs is None else np.asarray(t_obs, dtype=np.float64).reshape(-1)
+    beta, gamma = float(theta[0]), float(theta[1])
+    N = S0 + I0 + R0
+    S, I, t, k = int(S0), int(I0), 0.0, 0
+    I_obs = np.empty(len(t_obs))
+    while t < t_max and I > 0:
+        infection_rate, recovery_rate = beta * S * I / N, gamma * I
+        total_rate = infection_rate + recovery_rate
+        if not total_rate > 0.0:
+            break
+        t += rng.exponential(1.0 / total_rate)
+        while k < len(t_obs) and t_obs[k] < t:
+            I_obs[k] = I
+            k += 1
+        if rng.random() < infection_rate / total_rate:
+            S, I = S - 1, I + 1
+        else:
+            I -= 1
+    I_obs[k:] = I
+    return t_obs, I_obs
+
+
 def sir_observation(theta=(0.3, 0.1), S0=99, I0=1, R0=0, t_max=160.0, seed=123):
     """An observation for `StochasticSIR` made the way the reference's documentation makes one (docs/src/example.md:75-148):
     one Gillespie run at theta = (beta, gamma) with NumPy's generator, summarised as

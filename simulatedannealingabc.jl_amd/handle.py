@@ -56,13 +56,20 @@ class SabcHandle:
             raise SABCError(rc, self._L.sabc_last_global_error().decode("utf-8", "replace"))
         self._h = h
         self._keep = []   # ctypes callbacks must outlive the handle
-        self._host_model = None
+        self._host_model = self._host_prior = None
+        self._validate_data = getattr(model, "validate_data", None)    # a DeviceSource's own requirements of its data
         if getattr(model, "model_id", None) == _lib.MODEL_USER:
             rc = self._L.sabc_register_device_simulator(self._h, model.source.encode())
             if rc:
                 msg = self._L.sabc_last_error(self._h).decode("utf-8", "replace")
                 self.close()
                 raise SABCError(rc, msg)
+            if getattr(model, "data", None) is not None:     # the observations the model was constructed with
+                try:
+                    self.set_data(model.data)
+                except Exception:
+                    self.close()
+                    raise
         self._host_prior = None
         if getattr(prior, "host_prior", False):
             cbs = prior.callbacks()
@@ -127,6 +134,23 @@ class SabcHandle:
         a.history_phase, a.more_chunks_follow = int(history_phase), int(bool(more_chunks_follow))
         a.proposal_kind, a.proposal_p0, a.proposal_p1 = proposal.descriptor()
         self._check(self._L.sabc_update(self._h, C.byref(a)))
+
+    def set_data(self, data):
+        """The observed data a simulator from source reads through sabc::data*() (sabc_set_device_data): one array-like, or a
+        sequence of array-likes with one segment each; None or an empty array drops them.  Copied to device memory the handle
+        owns; legal between any two calls -- the next update sees the new data, nothing is compiled."""
+        from .models import data_segments
+        segs = [] if data is None else data_segments(data)
+        if segs and self._validate_data is not None:
+            self._validate_data(segs)                     # e.g. segments of equal length: the source checks no index
+        flat = np.ascontiguousarray(np.concatenate(segs) if segs else np.zeros(0), dtype=np.float64)
+        lens = (C.c_int64 * max(len(segs), 1))(*[len(s) for s in segs])
+        self._check(self._L.sabc_set_device_data(self._h, _dp(flat), len(flat), lens, len(segs)))
+
+    @property
+    def data_len(self):
+        """Doubles of observed data the handle holds on the device (all segments)."""
+        return int(self._L.sabc_device_data_len(self._h))
 
     def set_stream(self, hip_stream: int):
         self._check(self._L.sabc_set_stream(self._h, C.c_void_p(hip_stream)))

@@ -20,7 +20,8 @@ import Dates
 import Base: show
 
 export sabc, update_population!, RandomWalk, DifferentialEvolution, StretchMove,
-       DeviceDistance, GaussianIID, Gaussian2D, GandK, LotkaVolterra, DeviceSource, StochasticSIR, SourcePrior, comm_unique_id
+       DeviceDistance, GaussianIID, Gaussian2D, GandK, LotkaVolterra, DeviceSource, StochasticSIR, NormalMoments, StochasticSIRSeries, SourcePrior,
+       comm_unique_id
 
 const libsabc = get(ENV, "SABC_HIP_LIB", joinpath(@__DIR__, "..", "libsabc_hip.so"))
 
@@ -139,14 +140,68 @@ model_id(::HostDistance) = Int32(0)
 
 # ---- f_dist as HIP source, compiled at run time into the fused update kernel (include/sabc_hip.h:
 #      sabc_register_device_simulator); with a SourcePrior the same source also defines the prior (prior_joint = 3).
-#      n_stats <= 64; observations belong in the source (a __constant__ array), params holds at most 32 values ----
+#      n_stats <= 64; params holds at most 32 values.  Observations are `data`: one array or a tuple / vector of arrays, one
+#      segment each (at most 8), kept in device memory by the handle (sabc_set_device_data) and read by the source through
+#      sabc::data_len(segment) / sabc::data_at(i, segment); an array of several dimensions is flattened in Julia's own
+#      (column-major) order.  With `data_names = (:y_obs, :t_obs)`, `sabc` and `update_population!` take that many extra
+#      positional arguments or keywords of those names, as the reference forwards args... / kwargs... to f_dist (:164,175,315):
+#      they become the segments in that order; in `update_population!` data that are not given leave the handle's ----
 struct DeviceSource <: DeviceDistance
     source::String
     n_para::Int
     n_stats::Int
     params::Vector{Float64}
+    data::Vector{Vector{Float64}}
+    data_names::Tuple
+    validate::Function                   # segments -> nothing, or throws: what this model's source requires of its data
 end
-DeviceSource(source, n_para, n_stats; params=Float64[]) = DeviceSource(source, n_para, n_stats, collect(Float64, params))
+no_data_check(segs) = nothing
+data_segment(x) = vec(collect(Float64, x))
+data_segments(x) = x === nothing ? Vector{Float64}[] :
+                   (x isa Tuple || (x isa Vector && !(eltype(x) <: Real))) ? Vector{Float64}[data_segment(y) for y in x] :
+                   Vector{Float64}[data_segment(x)]
+function DeviceSource(source, n_para, n_stats; params=Float64[], data=nothing, data_names=(), validate=no_data_check)
+    segs = data_segments(data)
+    isempty(segs) || validate(segs)
+    length(segs) <= 8 || throw(ArgumentError("at most 8 data segments"))
+    names = Tuple(Symbol(n) for n in data_names)
+    (isempty(names) || isempty(segs) || length(names) == length(segs)) || throw(ArgumentError("one name in data_names per data segment"))
+    DeviceSource(source, n_para, n_stats, collect(Float64, params), segs, names, validate)
+end
+# the four positional arguments the struct took before it carried data (StochasticSIR, and callers' own code)
+DeviceSource(source, n_para, n_stats, params) = DeviceSource(source, n_para, n_stats; params=params)
+with_data(m::DeviceSource, segs) = DeviceSource(m.source, m.n_para, m.n_stats, m.params, segs, m.data_names, m.validate)
+
+# the extra arguments of sabc / update_population! as data segments in the order of data_names; nothing if there are none
+function bind_data(f_dist::DeviceDistance, kwargs)
+    isempty(kwargs) && return nothing
+    names = f_dist isa DeviceSource ? f_dist.data_names : ()
+    isempty(names) && throw(ArgumentError("a DeviceDistance takes its data at construction; extra args/kwargs are not forwarded"))
+    for k in keys(kwargs)
+        k in names || throw(ArgumentError("unexpected keyword argument $(k): data_names = $(names)"))
+    end
+    for k in names
+        haskey(kwargs, k) || throw(ArgumentError("missing data argument $(k): data_names = $(names)"))
+    end
+    segs = Vector{Float64}[data_segment(kwargs[k]) for k in names]
+    f_dist.validate(segs)                # the checks of the constructor, for data that arrive with the call
+    segs
+end
+# positional data -> keywords of the first names
+function positional_data(f_dist::DeviceSource, args, kwargs)
+    names = f_dist.data_names
+    length(args) <= length(names) || throw(ArgumentError("$(length(args)) positional data arguments given, data_names = $(names)"))
+    for k in names[1:length(args)]
+        haskey(kwargs, k) && throw(ArgumentError("data argument $(k) given both by position and by keyword: data_names = $(names)"))
+    end
+    NamedTuple{names[1:length(args)]}(args)
+end
+function set_device_data!(h::Ptr{Cvoid}, segs)
+    flat = reduce(vcat, segs; init=Float64[])
+    lens = Int64[length(s) for s in segs]
+    GC.@preserve flat lens check(h, ccall((:sabc_set_device_data, libsabc), Cint, (Ptr{Cvoid}, Ptr{Float64}, Int64, Ptr{Int64}, Int32),
+                                          h, flat, length(flat), lens, length(lens)))
+end
 model_id(::DeviceSource) = Int32(5)
 n_stats(m::DeviceSource) = m.n_stats
 params(m::DeviceSource) = m.params
@@ -170,6 +225,39 @@ function StochasticSIR(data_obs; t_max=160.0, n_stats::Integer=3, compartments..
     obs = Float64[data_obs.total_infected, data_obs.peak_infected, data_obs.t_peak]
     DeviceSource("#define SIR_N_STATS $(n_stats)\n" * text, 2, Int(n_stats), Float64[s0, i0, r0, t_max, obs...])
 end
+"""
+    NormalMoments(; y_obs=nothing)
+
+The `f_dist` of the reference's getting-started example (docs/src/usage.md:15-35) on the device: θ = (μ, σ), `length(y_obs)` draws
+of Normal(μ, σ), ρ = (|mean(y_obs) − mean(y_sim)|, |Σ y_obs² − Σ y_sim²|).  `y_obs` is data: give it here or, the reference's
+call shape, as `sabc(model, prior; y_obs=...)` / `update_population!(res, model, prior; y_obs=...)`.
+"""
+NormalMoments(; y_obs=nothing) =
+    DeviceSource(read(joinpath(@__DIR__, "..", "device_sources", "normal_moments.hip"), String), 2, 2;
+                 data=y_obs === nothing ? nothing : (y_obs,), data_names=(:y_obs,), validate=check_moments_data)
+check_moments_data(segs) = (length(segs) == 1 && length(segs[1]) >= 1) || throw(ArgumentError("y_obs holds at least one value"))
+
+"""
+    StochasticSIRSeries(; t_obs=nothing, I_obs=nothing, S0=99, I0=1, R0=0, t_max=160.0)
+
+The Gillespie epidemic of `StochasticSIR` compared with a whole observed curve: two data segments, `t_obs` (increasing) and
+`I_obs`; ρ = (mean_k |I(t_k) − I_obs[k]|,), I(t_k) the number infected just before the first event later than t_k.
+"""
+function StochasticSIRSeries(; t_obs=nothing, t_max=160.0, rest...)
+    # keywords I_obs and S0, I0, R0 (the reference's spelling), collected here so that the defaults sit next to their names
+    kw = values(rest)
+    i_obs = get(kw, :I_obs, nothing)
+    c = merge(NamedTuple{(Symbol("S0"), Symbol("I0"), Symbol("R0"))}((99, 1, 0)), Base.structdiff(kw, NamedTuple{(:I_obs,)}))
+    length(c) == 3 || throw(ArgumentError("unknown keyword: I_obs and the compartments S0, I0, R0"))
+    s0, i0, r0 = Int(c[1]), Int(c[2]), Int(c[3])
+    (s0 >= 0 && r0 >= 0 && i0 >= 1) || throw(ArgumentError("compartments must be non-negative, I0 at least 1"))
+    (t_obs === nothing) == (i_obs === nothing) || throw(ArgumentError("t_obs and I_obs come together"))
+    DeviceSource(read(joinpath(@__DIR__, "..", "device_sources", "sir_series.hip"), String), 2, 1; params=Float64[s0, i0, r0, t_max],
+                 data=t_obs === nothing ? nothing : (t_obs, i_obs), data_names=(:t_obs, :I_obs), validate=check_series_data)
+end
+# the source reads I_obs[k] for every k < length(t_obs): a shorter I_obs would be read past its end
+check_series_data(segs) = (length(segs) == 2 && length(segs[1]) == length(segs[2]) >= 1 && issorted(segs[1]; lt=<=)) ||
+    throw(ArgumentError("t_obs is increasing, holds at least one value and is as long as I_obs"))
 """
     SourcePrior(d)
 
@@ -360,6 +448,7 @@ function create_handle(f_dist::DeviceDistance, prior; n_particles, algorithm, v,
     end
     if f_dist isa DeviceSource
         check(h[], ccall((:sabc_register_device_simulator, libsabc), Cint, (Ptr{Cvoid}, Cstring), h[], f_dist.source))
+        isempty(f_dist.data) || set_device_data!(h[], f_dist.data)
     end
     if f_dist isa HostDistance
         cb = host_callback(f_dist)
@@ -484,10 +573,12 @@ function update_population!(res::SABCresult, f_dist::DeviceDistance, prior::Dist
                             proposal::Proposal=DifferentialEvolution(n_para=length(prior)),
                             resample=nothing, checkpoint_history=1,
                             show_progressbar::Bool=!is_logging(stderr),
-                            show_checkpoint=is_logging(stderr) ? 100 : Inf)
+                            show_checkpoint=is_logging(stderr) ? 100 : Inf, data...)
     v <= 0 && error("Annealing speed `v` must be positive.")                       # :261
     δ <= 0 && error("Resamping intensity `δ` must be positive.")                   # :262
     h = handle_of(res)[]
+    segs = bind_data(f_dist, data)                                                 # y_obs of this call, forwarded like :315
+    segs === nothing || set_device_data!(h, segs)
     d, s = length(prior), size(res.u, 2)
     n_global = ccall((:sabc_n_global, libsabc), Int64, (Ptr{Cvoid},), h)           # == length(population) on one GPU
     resample = something(resample, 2 * n_global)                                   # :255
@@ -535,6 +626,12 @@ function update_population!(res::SABCresult, f_dist::DeviceDistance, prior::Dist
     res
 end
 
+# data by position: update_population!(res, model, prior, y_obs; ...) -> the keywords of data_names
+update_population!(res::SABCresult, f_dist::DeviceSource, prior::Distribution, arg1, args...; kwargs...) =
+    update_population!(res, f_dist, prior; positional_data(f_dist, (arg1, args...), kwargs)..., kwargs...)
+sabc(f_dist::DeviceSource, prior::Distribution, arg1, args...; kwargs...) =
+    sabc(f_dist, prior; positional_data(f_dist, (arg1, args...), kwargs)..., kwargs...)
+
 # update_population!(res, f_dist, prior, args...; kwargs...) with the plain function the result was created
 # with (SimulatedAnnealingABC.jl:251): look the wrapped model up by handle; args/kwargs go to f_dist (:315)
 function update_population!(res::SABCresult, f_dist::Function, prior::Distribution, args...; kwargs...)
@@ -559,7 +656,7 @@ function sabc(f_dist::DeviceDistance, prior::Distribution;
               proposal::Proposal=DifferentialEvolution(n_para=length(prior)),
               resample=2 * n_particles, v=1.0, δ=0.1, checkpoint_history=1,
               show_progressbar::Bool=!is_logging(stderr), show_checkpoint=is_logging(stderr) ? 100 : Inf,
-              seed=nothing, device=0, rank=0, world=1, comm_id=nothing)
+              seed=nothing, device=0, rank=0, world=1, comm_id=nothing, data...)
     (algorithm == :multi_eps || algorithm == :single_eps) ||
         error("Argument `algorithm` must be :multi_eps or :single_eps, not `$algorithm`!")   # :462-464
     n_simulation < n_particles &&
@@ -567,6 +664,10 @@ function sabc(f_dist::DeviceDistance, prior::Distribution;
     world > 1 && isnothing(seed) && error("world > 1 needs an explicit `seed`: every shard must use the same Philox key")
     seed = something(seed, rand(UInt64) >> 1)
     @info "Initialization for '$(algorithm)'"                                                # :158
+    segs = bind_data(f_dist, data)                       # y_obs = ... replaces what the model was constructed with
+    segs === nothing || (f_dist = with_data(f_dist, segs))
+    f_dist isa DeviceSource && !isempty(f_dist.data_names) && isempty(f_dist.data) &&
+        throw(ArgumentError("the model has no data: give them at construction or to this call, data_names = $(f_dist.data_names)"))
     h = create_handle(f_dist, prior; n_particles, algorithm, v, δ, seed, device, rank, world, comm_id)
     check(h[], ccall((:sabc_initialize, libsabc), Cint, (Ptr{Cvoid}, Int64), h[], n_simulation))
     d, s = length(prior), n_stats(f_dist)

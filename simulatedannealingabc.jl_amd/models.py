@@ -135,6 +135,22 @@ class HostDistance(DeviceDistance):
         return _lib.SIMULATE_FN(cb)
 
 
+def _segment(a):
+    return np.ascontiguousarray(a, dtype=np.float64).reshape(-1)      # float64, flattened in C order
+
+
+def data_segments(data):
+    """`data` of a DeviceSource as a list of float64 vectors, one per segment: an array (of any shape) or a sequence of
+    numbers is ONE segment; a list or tuple holding array-likes is one segment per element."""
+    if isinstance(data, (list, tuple)) and any(np.ndim(x) > 0 for x in data):
+        segs = [_segment(x) for x in data]
+    else:
+        segs = [_segment(data)]
+    if len(segs) > _lib.MAX_DATA_SEGMENTS:
+        raise ValueError(f"at most {_lib.MAX_DATA_SEGMENTS} data segments")
+    return segs
+
+
 class DeviceSource(DeviceDistance):
     """`f_dist` as HIP source (SimulatedAnnealingABC.jl:164,175,315 for a simulator of your own ON the device):
 
@@ -154,17 +170,63 @@ class DeviceSource(DeviceDistance):
     calls are made (the bound is mandatory), the call returns their number and the stream has advanced by exactly that many
     blocks; a team of lanes generates a group of events side by side and drops the rest at the first false.  `params` is the `params` list given here.  The source is compiled at run time (hipRTC, gfx950) into
     the same fused propose -> simulate -> ECDF -> accept kernel as the built-in simulators.  n_stats <= 64 (_lib.MAX_SOURCE_STATS;
-    above 16 the wide form of the kernels).  `params` holds at most 32 values: observations the simulator compares
-    against (a time series) belong in the source itself, e.g. `__constant__ double kObs[48] = {...};`."""
+    above 16 the wide form of the kernels).  `params` holds at most 32 values.
+
+    Observations the simulator compares against (a time series) are `data`: one array-like, or a sequence of array-likes -- one
+    segment each, at most 8 --, float64, flattened in C order and kept in device memory by the handle.  The source -- the
+    simulator and, with a SourcePrior, the prior -- reads them with `sabc::data_len(segment = 0)`, `sabc::data_at(i, segment = 0)`
+    (through the constant address space: an index shared by the wave's lanes is one scalar load), `sabc::data(segment = 0)` (the
+    plain pointer; nullptr while nothing is set) and `sabc::data_segments()`; indices are not checked.  Another data set is another
+    `SabcHandle.set_data(...)`, never another source or another compilation.  With `data_names=("y_obs", "t_obs")`, `sabc`,
+    `initialization` and `update_population_` take that many extra positional arguments, or keywords of those names, the way
+    the reference hands `args...` / `kwargs...` to `f_dist`: they become the segments in the order of `data_names` and replace
+    what the model was constructed with (in `update_population_`: what the handle holds; data not given leave it)."""
     model_id = _lib.MODEL_USER
 
-    def __init__(self, hip_source: str, n_para: int, n_stats: int, params=()):
+    def __init__(self, hip_source: str, n_para: int, n_stats: int, params=(), data=None, data_names=None):
         self.source = str(hip_source)
         self.n_para = (int(n_para),)
         self.n_stats = int(n_stats)
         self._params = [float(p) for p in params]
         if len(self._params) > _lib.MAX_MODEL_PARAMS:
             raise ValueError(f"at most {_lib.MAX_MODEL_PARAMS} parameters")
+        self.data_names = None if data_names is None else tuple(str(x) for x in data_names)
+        if self.data_names is not None and not 1 <= len(self.data_names) <= _lib.MAX_DATA_SEGMENTS:
+            raise ValueError(f"data_names: 1 to {_lib.MAX_DATA_SEGMENTS} names, one per data segment")
+        self.data = None if data is None else data_segments(data)
+        if self.data is not None and self.data_names is not None and len(self.data) != len(self.data_names):
+            raise ValueError(f"data holds {len(self.data)} segments, data_names = {self.data_names!r} names {len(self.data_names)}")
+        if self.data is not None:
+            self.validate_data(self.data)
+
+    def validate_data(self, segments):
+        """What this model's source requires of its data (the source itself checks no index): called wherever data enter --
+        the constructor, the extra arguments of sabc / initialization / update_population_, and SabcHandle.set_data of a handle
+        made for this model.  Raises ValueError.  The base class accepts anything; the shipped models override it."""
+
+    def bind_data(self, args, kwargs):
+        """The extra arguments of sabc / initialization / update_population_ as data segments in the order of `data_names`;
+        None if there are none.  A wrong count or an unknown name is a TypeError naming `data_names`."""
+        if not args and not kwargs:
+            return None
+        if not self.data_names:
+            raise TypeError("a DeviceDistance takes its data at construction; extra args/kwargs are not forwarded "
+                            "(a DeviceSource takes them when it is constructed with data_names)")
+        names = self.data_names
+        unknown = sorted(set(kwargs) - set(names))
+        if unknown:
+            raise TypeError(f"unexpected keyword argument(s) {unknown}: data_names = {names!r}")
+        if len(args) > len(names):
+            raise TypeError(f"{len(args)} positional data arguments given, data_names = {names!r} takes {len(names)}")
+        twice = [n for n in names[:len(args)] if n in kwargs]
+        if twice:
+            raise TypeError(f"data argument(s) {twice} given both by position and by keyword: data_names = {names!r}")
+        missing = [n for n in names[len(args):] if n not in kwargs]
+        if missing:
+            raise TypeError(f"missing data argument(s) {missing}: data_names = {names!r}")
+        segments = [_segment(a) for a in (*args, *(kwargs[n] for n in names[len(args):]))]
+        self.validate_data(segments)
+        return segments
 
     @property
     def params(self):
@@ -217,3 +279,49 @@ class StochasticSIR(DeviceSource):
         self.t_max, self.data_obs = float(t_max), tuple(obs)
         super().__init__(f"#define SIR_N_STATS {int(n_stats)}\n" + device_source_text("sir"), 2, int(n_stats),
                          [*comp, self.t_max, *obs])
+
+
+class NormalMoments(DeviceSource):
+    """The `f_dist` of the reference's getting-started example (docs/src/usage.md:15-35) on the device: theta = (mu, sigma),
+    y_sim = len(y_obs) draws of Normal(mu, sigma), rho = (|mean(y_obs) - mean(y_sim)|, |sum(y_obs^2) - sum(y_sim^2)|).  `y_obs`
+    is data, not source text or parameters: give it here, or -- the reference's call shape -- to `sabc(model, prior,
+    y_obs=...)` and `update_population_(res, model, prior, y_obs=...)`.  Source: device_sources/normal_moments.hip."""
+
+    def __init__(self, y_obs=None, data_names=("y_obs",)):
+        super().__init__(device_source_text("normal_moments"), 2, 2, (), data=None if y_obs is None else [_segment(y_obs)],
+                         data_names=data_names)
+
+    def validate_data(self, segments):
+        if len(segments) != 1 or len(segments[0]) < 1:
+            raise ValueError("y_obs is one segment of at least one value (both distances divide by or sum over its length)")
+
+
+class StochasticSIRSeries(DeviceSource):
+    """The Gillespie epidemic of `StochasticSIR` compared with a whole observed curve: `t_obs` (increasing) and `I_obs` are two
+    data segments, rho = (mean_k |I(t_k) - I_obs[k]|,) with I(t_k) the number infected just before the first event later than
+    t_k (the final number once no event follows).  Source: device_sources/sir_series.hip; `examples.sir_series_observation`
+    simulates an observation on the host."""
+
+    def __init__(self, t_obs=None, I_obs=None, S0=99, I0=1, R0=0, t_max=160.0, data_names=("t_obs", "I_obs")):
+        comp = []
+        for name, v in (("S0", S0), ("I0", I0), ("R0", R0)):
+            if isinstance(v, bool) or float(v) != int(v) or int(v) < 0:
+                raise ValueError(f"{name} must be a non-negative integer, got {v!r}")
+            comp.append(int(v))
+        if comp[1] < 1:
+            raise ValueError("I0 must be at least 1: an epidemic without an infected individual has no events")
+        if (t_obs is None) != (I_obs is None):
+            raise ValueError("t_obs and I_obs come together")
+        data = None
+        if t_obs is not None:
+            data = [_segment(t_obs), _segment(I_obs)]
+        self.S0, self.I0, self.R0 = comp
+        self.t_max = float(t_max)
+        super().__init__(device_source_text("sir_series"), 2, 1, [*comp, self.t_max], data=data, data_names=data_names)
+
+    def validate_data(self, segments):
+        # the source reads I_obs[k] for every k < len(t_obs): a shorter I_obs would be read past its end on the device
+        if len(segments) != 2 or len(segments[0]) != len(segments[1]) or len(segments[0]) < 1:
+            raise ValueError("t_obs and I_obs hold the same number of values, at least one")
+        if np.any(np.diff(segments[0]) <= 0):
+            raise ValueError("t_obs must be increasing")
