@@ -302,11 +302,13 @@ int HipBackend::register_device_simulator(const char *hip_source) {
   std::string log;
   // (the one-launch form of small shards -- k_update_persistent -- is compiled only for handles that can take it)
   const bool small = persist_.max > 0 && sh_.world == 1 && sh_.n_local <= persist_.max && persistent_fits(m_.d, m_.s);
-  if (rtc_build(hip_source, m_.d, m_.s, rtc_default_csrc_dir(), &rtc_, &log, m_.prior_joint == 3, small)) {
+  RtcRequest rq{hip_source, m_.d, m_.s, rtc_default_csrc_dir(), /*user_prior=*/m_.prior_joint == 3, /*with_persistent=*/small};
+  if (rtc_compile(rq, &rtc_, &log)) {
     // the one-launch kernels are the largest of the unit (three team widths x three proposals): should the compiler give up on
     // them for this simulator, the launch chain alone still runs it -- only a source that fails there too is an error
     std::string log_chain;
-    if (!small || rtc_build(hip_source, m_.d, m_.s, rtc_default_csrc_dir(), &rtc_, &log_chain, m_.prior_joint == 3, false)) {
+    rq.with_persistent = false;
+    if (!small || rtc_compile(rq, &rtc_, &log_chain)) {
       err_ = "compiling the device simulator failed:\n" + log;
       return -1;
     }

@@ -151,31 +151,28 @@ int64_t persistent_workgroups(const ModelDesc &m, int prop_kind, int64_t act_n, 
   if (lanes_out) *lanes_out = 1;
   if (active_out) *active_out = (int)B;
   if (prop_kind < 0 || prop_kind > 2 || act_n < 2) return 0;
-  bool have4 = true, have16 = true;
-  if (m.model_id == SABC_MODEL_USER) {                 // a simulator from source: compiled with it (rtc.cpp), where its shape fits
-    if (!rtc || !rtc->persistent[prop_kind]) return 0;
-    have4 = rtc->persistent4[prop_kind] != nullptr;
-    have16 = rtc->persistent16[prop_kind] != nullptr;
-  } else if (!(m.model_id == SABC_MODEL_GAUSS_IID || m.model_id == SABC_MODEL_GAUSS2D || m.model_id == SABC_MODEL_LV)) {
+  const bool user = m.model_id == SABC_MODEL_USER;     // a simulator from source: compiled with it (rtc.cpp), where its shape fits
+  if (user ? !rtc || !rtc->persistent[0][prop_kind]
+           : !(m.model_id == SABC_MODEL_GAUSS_IID || m.model_id == SABC_MODEL_GAUSS2D || m.model_id == SABC_MODEL_LV))
     return 0;
-  }
   if (!persistent_fits(m.d, m.s)) return 0;
   const int64_t per_launch = prop_kind == SABC_PROP_RANDOMWALK ? act_n : act_n - act_n / 2;     // the larger half batch
   // a wave per SIMD at most, and one wave of the workgroup without particles: the control wave (persistent_kernel.hpp)
   const int64_t thin = B - 64 < 256 ? B - 64 : 256;
   const int want = persist_lanes_env();
-  const bool may16 = have16 && (want == 16 || (want == 0 && per_launch <= persist_team_max_particles(16)));
-  const bool may4 = have4 && (want == 4 || want == 16 || (want == 0 && per_launch <= persist_team_max_particles(4)));
+  const bool may[3] = {true, want == 4 || want == 16 || (want == 0 && per_launch <= persist_team_max_particles(4)),
+                       want == 16 || (want == 0 && per_launch <= persist_team_max_particles(16))};
   // the thinnest spread whose workgroups fit the launch: a row per particle before a quad before a lane, a wave per SIMD before
   // the whole block
-  const int64_t lanes_try[6] = {16, 16, 4, 4, 1, 1}, active_try[6] = {thin, B, thin, B, thin, B};
-  for (int i = 0; i < 6; ++i) {
-    if ((lanes_try[i] == 16 && !may16) || (lanes_try[i] == 4 && !may4)) continue;
-    const int64_t wg = (lanes_try[i] * per_launch + active_try[i] - 1) / active_try[i];
-    if (wg > persist_max_workgroups()) continue;
-    if (lanes_out) *lanes_out = (int)lanes_try[i];
-    if (active_out) *active_out = (int)active_try[i];
-    return wg;
+  for (int team = 2; team >= 0; --team) {
+    if (!may[team] || (user && !rtc->persistent[team][prop_kind])) continue;
+    for (const int64_t active : {thin, B}) {
+      const int64_t wg = (kPersistTeamLanes[team] * per_launch + active - 1) / active;
+      if (wg > persist_max_workgroups()) continue;
+      if (lanes_out) *lanes_out = kPersistTeamLanes[team];
+      if (active_out) *active_out = (int)active;
+      return wg;
+    }
   }
   return 0;
 }
@@ -204,8 +201,8 @@ int launch_update_persistent(const ModelDesc &m, int prop_kind, const PersistArg
   pa.ctrl_wave = active < (int)update_block_threads(m.s) ? active / 64 : -1;
   const dim3 grid((unsigned)wg), block((unsigned)update_block_threads(m.s));
   if (m.model_id == SABC_MODEL_USER)
-    return module_launch(lanes == 16 ? rtc->persistent16[prop_kind] : lanes == 4 ? rtc->persistent4[prop_kind] : rtc->persistent[prop_kind], grid.x, block.x, stream, nullptr, nullptr, m, pa,
-                         cb, pp, cdf, pv_a, pv_b, partials, hist, mbox, stage);
+    return module_launch(rtc->persistent[persist_team(lanes)][prop_kind], grid.x, block.x, stream, nullptr, nullptr, m, pa, cb, pp, cdf,
+                         pv_a, pv_b, partials, hist, mbox, stage);
   auto launch = [&](auto kernel) {
     hipLaunchKernelGGL(kernel, grid, block, 0, stream, m, pa, cb, pp, cdf, pv_a, pv_b, partials, hist, mbox, stage);
   };

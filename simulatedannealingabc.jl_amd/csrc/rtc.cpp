@@ -6,6 +6,7 @@
 #include <sys/stat.h>
 #include <unistd.h>
 
+#include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -67,7 +68,7 @@ void anchor() {}
 // sabc() call makes one) loads the module without paying the ~2 s of compilation again
 struct CachedModule {
   std::vector<char> code;
-  std::string lowered[16];
+  std::vector<std::string> lowered;                    // one per entry of kernel_table()
 };
 std::mutex g_cache_mutex;
 std::map<std::string, CachedModule> g_cache;
@@ -85,28 +86,59 @@ uint64_t fnv1a(const void *data, size_t n, uint64_t h) {
   return h;
 }
 
-uint64_t headers_hash(const std::string &csrc_dir) {
+// The headers of the unit are FOUND, not listed: from the two the unit names, every file an #include "..." line names, looked
+// for next to the including file and then in csrc_dir; depth first in order of appearance, each file once, its name as written
+// and then its text into the hash.  Conditionals are not evaluated: a superset of what the compiler reads (rtc.hpp comes in
+// through kernels.hpp), never less -- text that moves into a new header is covered without anybody remembering a list.
+// <...> includes (ROCm, the C++ library) are not followed.  A file that cannot be opened contributes its name only.
+struct UnitHeaders {
+  std::vector<std::string> paths;                      // in order of the visit
+  std::vector<std::pair<dev_t, ino_t>> files;          // those that opened: each once, by whichever route it is reached
+  uint64_t hash = 14695981039346656037ull;
+};
+
+void scan_header(const std::string &name, const std::string &from_dir, const std::string &csrc_dir, UnitHeaders *u) {
+  std::string path = from_dir + "/" + name;
+  FILE *fp = std::fopen(path.c_str(), "rb");
+  if (!fp) { path = csrc_dir + "/" + name; fp = std::fopen(path.c_str(), "rb"); }
+  struct stat st = {};
+  if (fp) (void)::fstat(fileno(fp), &st);
+  const std::pair<dev_t, ino_t> id(st.st_dev, st.st_ino);
+  if (fp ? std::count(u->files.begin(), u->files.end(), id) : std::count(u->paths.begin(), u->paths.end(), path)) {
+    if (fp) std::fclose(fp);
+    return;
+  }
+  u->paths.push_back(path);
+  u->hash = fnv1a(name.data(), name.size(), u->hash);
+  if (!fp) return;
+  u->files.push_back(id);
+  std::string text((size_t)st.st_size, '\0');
+  text.resize(std::fread(&text[0], 1, text.size(), fp));
+  std::fclose(fp);
+  u->hash = fnv1a(text.data(), text.size(), u->hash);
+  const std::string dir = path.substr(0, path.rfind('/'));
+  const auto blank = [&](size_t i) { return text[i] == ' ' || text[i] == '\t'; };
+  for (size_t at = text.find('#'); at != std::string::npos; at = text.find('#', at + 1)) {
+    size_t i = at;                                     // # include "name", with nothing but blanks ahead of it on its line
+    while (i > 0 && blank(i - 1)) --i;
+    if (i > 0 && text[i - 1] != '\n') continue;
+    size_t q = text.find_first_not_of(" \t", at + 1);
+    if (q == std::string::npos || text.compare(q, 7, "include") != 0) continue;
+    q = text.find_first_not_of(" \t", q + 7);
+    const size_t e = q == std::string::npos ? q : text.find_first_of("\"\n", q + 1);
+    if (e != std::string::npos && text[q] == '"' && text[e] == '"') scan_header(text.substr(q + 1, e - q - 1), dir, csrc_dir, u);
+  }
+}
+
+const UnitHeaders &unit_headers(const std::string &csrc_dir) {
   static std::mutex m;
-  static std::map<std::string, uint64_t> memo;
+  static std::map<std::string, UnitHeaders> memo;
   std::lock_guard<std::mutex> lock(m);
   auto hit = memo.find(csrc_dir);
   if (hit != memo.end()) return hit->second;
-  static const char *files[] = {"update_kernel.hpp", "persistent_kernel.hpp", "device_models.hpp", "device_rng.hpp", "rng_tables.inc",
-                                "kernels.hpp", "control.hpp", "host_math.hpp", "prior_math.hpp", "sabc_types.hpp", "p2p.hpp",
-                                "../../include/sabc_hip.h"};
-  uint64_t h = 14695981039346656037ull;
-  for (const char *f : files) {
-    const std::string path = csrc_dir + "/" + f;
-    FILE *fp = std::fopen(path.c_str(), "rb");
-    h = fnv1a(f, std::strlen(f), h);
-    if (!fp) continue;
-    char buf[1 << 14];
-    size_t k;
-    while ((k = std::fread(buf, 1, sizeof(buf), fp)) > 0) h = fnv1a(buf, k, h);
-    std::fclose(fp);
-  }
-  memo[csrc_dir] = h;
-  return h;
+  UnitHeaders u;
+  for (const char *root : {"update_kernel.hpp", "persistent_kernel.hpp"}) scan_header(root, csrc_dir, csrc_dir, &u);
+  return memo.emplace(csrc_dir, std::move(u)).first->second;
 }
 
 std::string disk_cache_dir() {
@@ -125,7 +157,7 @@ std::string disk_cache_path(const std::string &cache_key, const std::string &csr
   const std::string dir = disk_cache_dir();
   if (dir.empty()) return dir;
   uint64_t h = fnv1a(cache_key.data(), cache_key.size(), 14695981039346656037ull);
-  const uint64_t hh = headers_hash(csrc_dir);
+  const uint64_t hh = unit_headers(csrc_dir).hash;
   const int abi = SABC_ABI_VERSION;
   h = fnv1a(&hh, sizeof(hh), h);
   h = fnv1a(&abi, sizeof(abi), h);
@@ -142,6 +174,7 @@ bool disk_cache_load(const std::string &path, int n_kernels, CachedModule *out) 
   if (!fp) return false;
   bool ok = false;
   uint64_t head[3] = {0, 0, 0};                        // magic, kernels, code bytes
+  out->lowered.assign((size_t)n_kernels, std::string());
   if (std::fread(head, sizeof(head), 1, fp) == 1 && head[0] == kDiskMagic && head[1] == (uint64_t)n_kernels && head[2] > 0 &&
       head[2] < ((uint64_t)1 << 30)) {
     ok = true;
@@ -158,17 +191,17 @@ bool disk_cache_load(const std::string &path, int n_kernels, CachedModule *out) 
   return ok;
 }
 
-void disk_cache_store(const std::string &path, int n_kernels, const CachedModule &m) {
+void disk_cache_store(const std::string &path, const CachedModule &m) {
   char tmp[32];
   std::snprintf(tmp, sizeof(tmp), ".%d.tmp", (int)getpid());
   const std::string t = path + tmp;
   FILE *fp = std::fopen(t.c_str(), "wb");
   if (!fp) return;
-  const uint64_t head[3] = {kDiskMagic, (uint64_t)n_kernels, (uint64_t)m.code.size()};
+  const uint64_t head[3] = {kDiskMagic, (uint64_t)m.lowered.size(), (uint64_t)m.code.size()};
   bool ok = std::fwrite(head, sizeof(head), 1, fp) == 1;
-  for (int i = 0; ok && i < n_kernels; ++i) {
-    const uint32_t len = (uint32_t)m.lowered[i].size();
-    ok = std::fwrite(&len, sizeof(len), 1, fp) == 1 && std::fwrite(m.lowered[i].data(), 1, len, fp) == len;
+  for (const std::string &name : m.lowered) {
+    const uint32_t len = (uint32_t)name.size();
+    ok = ok && std::fwrite(&len, sizeof(len), 1, fp) == 1 && std::fwrite(name.data(), 1, len, fp) == len;
   }
   ok = ok && std::fwrite(m.code.data(), 1, m.code.size(), fp) == m.code.size();
   const uint64_t tail = kDiskMagic ^ head[2];
@@ -210,6 +243,83 @@ __device__ __forceinline__ double data_at(long long i, int segment = 0) {
 }  // namespace sabc
 )SABC";
 
+// ... and behind it: the simulator the kernel templates of the unit are instantiated with
+const char kUserSimTail[] = R"SABC(
+namespace sabc {
+template <int D, int S>
+struct Sim<SABC_MODEL_USER, D, S> {
+  static __device__ __forceinline__ void run(const ModelDesc &m, const double *th, uint64_t pid, uint64_t iter,
+                                             double *rho, int coop = 0) {
+    NormalStream ns(m.seed, pid, PURPOSE_SIM, iter, coop);
+    ::sabc_user_simulate(th, m.p, ns, rho);
+  }
+};
+}  // namespace sabc
+)SABC";
+
+// ---- the kernels of a unit: THE table ----
+// Name expression (what hipRTC instantiates) and slot of `k` per kernel.  Everything that walks the kernels -- the name
+// expressions, the lowered names of a cached module, the resolution of the slots, their number -- walks this, in this order;
+// cache files and code objects depend on it.  More than kNarrowStats statistics: the wide kernels in the slots of the narrow
+// ones and the launch chain only (persistent_fits is false there).
+struct KernelEntry {
+  std::string name;
+  hipFunction_t *slot;
+};
+
+bool one_launch(int s, bool with_persistent) { return with_persistent && !source_wide(s); }
+
+std::vector<KernelEntry> kernel_table(int d, int s, bool with_persistent, RtcKernels *k) {
+  const std::string w = source_wide(s) ? "_wide" : "", ds = std::to_string(d) + ", " + std::to_string(s);
+  const std::string mds = std::to_string((int)SABC_MODEL_USER) + ", " + ds;
+  std::vector<KernelEntry> t;
+  t.push_back({"sabc::k_prior_simulate" + w + "<" + mds + ">", &k->prior_simulate});
+  for (int p = 0; p < 3; ++p) t.push_back({"sabc::k_update" + w + "<" + mds + ", " + std::to_string(p) + ">", &k->update[p]});
+  t.push_back({"sabc::k_simulate_batch" + w + "<" + mds + ">", &k->simulate_batch});
+  t.push_back({"sabc::k_stats" + w + "<" + ds + ">", &k->stats});
+  t.push_back({"sabc::k_prior_op_t<" + std::to_string(d) + ">", &k->prior_op});
+  if (one_launch(s, with_persistent))
+    for (int team = 0; team < 3; ++team) {             // (a lane per particle is the template's default: named without it, as ever)
+      const std::string lanes = team ? ", " + std::to_string(kPersistTeamLanes[team]) : "";
+      for (int p = 0; p < 3; ++p)
+        t.push_back({"sabc::k_update_persistent<" + mds + ", " + std::to_string(p) + lanes + ">", &k->persistent[team][p]});
+    }
+  return t;
+}
+
+// a code object into a module of its own with every slot of the table resolved, or nothing loaded and the reason in `log`
+bool load_kernels(const CachedModule &m, const RtcRequest &rq, RtcKernels *out, std::string *log) {
+  RtcKernels k;
+  if (hipModuleLoadData(&k.module, m.code.data()) != hipSuccess) { *log = "hipModuleLoadData of the simulator's code object failed"; return false; }
+  const std::vector<KernelEntry> table = kernel_table(rq.d, rq.s, rq.with_persistent, &k);
+  for (size_t i = 0; i < table.size(); ++i)
+    if (i >= m.lowered.size() || hipModuleGetFunction(table[i].slot, k.module, m.lowered[i].c_str()) != hipSuccess) {
+      *log = "kernel not found in the simulator's module: " + table[i].name;
+      rtc_release(&k);
+      return false;
+    }
+  *out = k;
+  return true;
+}
+
+// The launch geometry the host library was built with (launch_update, build_coarse) must be the one the kernels are compiled
+// for: a variant library (tools/build_variants.sh) forwards its -D overrides to the run-time compiler.  The same strings are
+// part of the cache key: a variant library must not find another's code.
+#define SABC_RTC_STR2(x) #x
+#define SABC_RTC_STR(x) SABC_RTC_STR2(x)
+#define SABC_RTC_DEFINE(x) "-D" #x "=" SABC_RTC_STR(x)
+const char *const kGeometry[6] = {SABC_RTC_DEFINE(SABC_UPDATE_BLOCK),  SABC_RTC_DEFINE(SABC_UPDATE_BLOCK_MS),  SABC_RTC_DEFINE(SABC_CDF_COARSE),
+                                  SABC_RTC_DEFINE(SABC_CDF_COARSE_MS), SABC_RTC_DEFINE(SABC_UPDATE_MIN_WAVES), SABC_RTC_DEFINE(SABC_UPDATE_MIN_WAVES_MS)};
+#undef SABC_RTC_DEFINE
+#undef SABC_RTC_STR
+#undef SABC_RTC_STR2
+
+struct Program {                                       // the hipRTC program, destroyed on every way out
+  HiprtcApi *api;
+  void *p = nullptr;
+  ~Program() { if (p) api->DestroyProgram(&p); }
+};
+
 }  // namespace
 
 const char *rtc_data_symbol() { return "sabc_data_desc"; }
@@ -229,124 +339,67 @@ void rtc_release(RtcKernels *k) {
   if (k) *k = RtcKernels();
 }
 
-int rtc_build(const char *user_source, int d, int s, const std::string &csrc_dir, RtcKernels *out, std::string *log,
-              bool user_prior, bool with_persistent) {
-  return rtc_compile(user_source, d, s, csrc_dir, out, log, nullptr, user_prior, with_persistent);
+std::vector<std::string> rtc_kernel_names(int d, int s, bool with_persistent) {
+  RtcKernels unused;
+  std::vector<std::string> names;
+  for (const KernelEntry &e : kernel_table(d, s, with_persistent, &unused)) names.push_back(e.name);
+  return names;
 }
 
-// out == nullptr: compile only (needs no device); code_size (optional) receives the size of the code object
-int rtc_compile(const char *user_source, int d, int s, const std::string &csrc_dir, RtcKernels *out, std::string *log,
-                size_t *code_size, bool user_prior, bool with_persistent) {
-  constexpr int kMaxKernels = 16;
-  // more than kNarrowStats statistics: the wide kernels in the slots of the narrow ones, the launch chain only
-  const bool wide = source_wide(s);
-  if (wide) with_persistent = false;
-  const int kKernels = with_persistent ? 16 : 7;
+std::vector<std::string> rtc_unit_headers(const std::string &csrc_dir, uint64_t *hash) {
+  const UnitHeaders &u = unit_headers(csrc_dir);
+  if (hash) *hash = u.hash;
+  return u.paths;
+}
+
+int rtc_compile(const RtcRequest &rq, RtcKernels *out, std::string *log, size_t *code_size) {
   HiprtcApi *api = hiprtc_api();
   if (!api) { *log = "libhiprtc.so could not be loaded: simulators from source need the hipRTC of ROCm"; return -1; }
-  if (d < 1 || d > SABC_MAX_PARA || s < 1 || s > SABC_MAX_SOURCE_STATS) { *log = "n_para / n_stats out of range (a simulator from source: d <= 16, s <= 64)"; return -1; }
-  char tail[2048];
-  std::snprintf(tail, sizeof(tail),
-                "\nnamespace sabc {\n"
-                "template <int D, int S>\n"
-                "struct Sim<SABC_MODEL_USER, D, S> {\n"
-                "  static __device__ __forceinline__ void run(const ModelDesc &m, const double *th, uint64_t pid, uint64_t iter,\n"
-                "                                             double *rho, int coop = 0) {\n"
-                "    NormalStream ns(m.seed, pid, PURPOSE_SIM, iter, coop);\n"
-                "    ::sabc_user_simulate(th, m.p, ns, rho);\n"
-                "  }\n"
-                "};\n"
-                "}  // namespace sabc\n");
-  std::string src = std::string("#include \"update_kernel.hpp\"\n") + (with_persistent ? "#include \"persistent_kernel.hpp\"\n" : "") + kDataPreamble + "#line 1 \"f_dist.hip\"\n";
-  src += user_source;
-  src += tail;
-
-  char name[kMaxKernels][112];
-  const char *w = wide ? "_wide" : "";
-  std::snprintf(name[0], sizeof(name[0]), "sabc::k_prior_simulate%s<%d, %d, %d>", w, SABC_MODEL_USER, d, s);
-  for (int p = 0; p < 3; ++p) std::snprintf(name[1 + p], sizeof(name[1 + p]), "sabc::k_update%s<%d, %d, %d, %d>", w, SABC_MODEL_USER, d, s, p);
-  std::snprintf(name[4], sizeof(name[4]), "sabc::k_simulate_batch%s<%d, %d, %d>", w, SABC_MODEL_USER, d, s);
-  std::snprintf(name[5], sizeof(name[5]), "sabc::k_stats%s<%d, %d>", w, d, s);
-  std::snprintf(name[6], sizeof(name[6]), "sabc::k_prior_op_t<%d>", d);
-  for (int p = 0; p < 3; ++p) std::snprintf(name[7 + p], sizeof(name[7 + p]), "sabc::k_update_persistent<%d, %d, %d, %d>", SABC_MODEL_USER, d, s, p);
-  for (int p = 0; p < 3; ++p) std::snprintf(name[10 + p], sizeof(name[10 + p]), "sabc::k_update_persistent<%d, %d, %d, %d, 4>", SABC_MODEL_USER, d, s, p);
-  for (int p = 0; p < 3; ++p) std::snprintf(name[13 + p], sizeof(name[13 + p]), "sabc::k_update_persistent<%d, %d, %d, %d, 16>", SABC_MODEL_USER, d, s, p);
+  if (rq.d < 1 || rq.d > SABC_MAX_PARA || rq.s < 1 || rq.s > SABC_MAX_SOURCE_STATS) { *log = "n_para / n_stats out of range (a simulator from source: d <= 16, s <= 64)"; return -1; }
+  const bool persistent = one_launch(rq.s, rq.with_persistent);
+  std::string src = std::string("#include \"update_kernel.hpp\"\n") + (persistent ? "#include \"persistent_kernel.hpp\"\n" : "") + kDataPreamble + "#line 1 \"f_dist.hip\"\n";
+  src += rq.source;
+  src += kUserSimTail;
+  RtcKernels unused;
+  const std::vector<KernelEntry> table = kernel_table(rq.d, rq.s, persistent, &unused);
   // extra compiler flags (e.g. -DSABC_NO_BITOP3: the two-instruction form of the Philox round's three-input XOR)
   const char *extra_env = std::getenv("SABC_RTC_EXTRA_FLAGS");
   const std::string extra = extra_env ? extra_env : "";
+  std::string cache_key = std::to_string(rq.d) + "," + std::to_string(rq.s) + (rq.user_prior ? ",P" : "") + (persistent ? ",1L4L16" : "") + "," + extra;
+  for (const char *g : kGeometry) cache_key += std::string(",") + g;
+  cache_key += std::string("\n") + kDataPreamble + "\n" + rq.source;
 
-  // (the launch geometry the library was built with is part of what is compiled: a variant library must not find another's code)
-#define SABC_RTC_STR2(x) #x
-#define SABC_RTC_STR(x) SABC_RTC_STR2(x)
-  static const char *geometry = SABC_RTC_STR(SABC_UPDATE_BLOCK) "," SABC_RTC_STR(SABC_UPDATE_BLOCK_MS) "," SABC_RTC_STR(SABC_CDF_COARSE) ","
-                                SABC_RTC_STR(SABC_CDF_COARSE_MS) "," SABC_RTC_STR(SABC_UPDATE_MIN_WAVES) "," SABC_RTC_STR(SABC_UPDATE_MIN_WAVES_MS);
-#undef SABC_RTC_STR
-#undef SABC_RTC_STR2
-  const std::string cache_key = std::to_string(d) + "," + std::to_string(s) + (user_prior ? ",P" : "") + (with_persistent ? ",1L4L16" : "") + "," + extra + "," +
-                                geometry + "\n" + kDataPreamble + "\n" + user_source;
-  if (out) {
+  if (out) {                                           // this process has compiled it: a failure here is an error
     std::lock_guard<std::mutex> lock(g_cache_mutex);
     auto hit = g_cache.find(cache_key);
     if (hit != g_cache.end()) {
-      RtcKernels k;
-      k.d = d; k.s = s;
-      if (hipModuleLoadData(&k.module, hit->second.code.data()) != hipSuccess) { *log = "hipModuleLoadData of the cached simulator failed"; return -1; }
-      hipFunction_t *slots[kMaxKernels] = {&k.prior_simulate, &k.update[0], &k.update[1], &k.update[2], &k.simulate_batch, &k.stats, &k.prior_op,
-                                        &k.persistent[0], &k.persistent[1], &k.persistent[2], &k.persistent4[0], &k.persistent4[1], &k.persistent4[2],
-                                        &k.persistent16[0], &k.persistent16[1], &k.persistent16[2]};
-      for (int i = 0; i < kKernels; ++i)
-        if (hipModuleGetFunction(slots[i], k.module, hit->second.lowered[i].c_str()) != hipSuccess) {
-          *log = std::string("kernel not found in the cached module: ") + name[i];
-          rtc_release(&k);
-          return -1;
-        }
+      if (!load_kernels(hit->second, rq, out, log)) return -1;
       if (code_size) *code_size = hit->second.code.size();
-      *out = k;
       return 0;
     }
   }
-  const std::string disk_path = out ? disk_cache_path(cache_key, csrc_dir) : std::string();
-  if (out && !disk_path.empty()) {
-    CachedModule entry;
-    if (disk_cache_load(disk_path, kKernels, &entry)) {
-      RtcKernels k;
-      k.d = d; k.s = s;
-      bool ok = hipModuleLoadData(&k.module, entry.code.data()) == hipSuccess;
-      hipFunction_t *slots[kMaxKernels] = {&k.prior_simulate, &k.update[0], &k.update[1], &k.update[2], &k.simulate_batch, &k.stats, &k.prior_op,
-                                           &k.persistent[0], &k.persistent[1], &k.persistent[2], &k.persistent4[0], &k.persistent4[1], &k.persistent4[2],
-                                        &k.persistent16[0], &k.persistent16[1], &k.persistent16[2]};
-      for (int i = 0; ok && i < kKernels; ++i) ok = hipModuleGetFunction(slots[i], k.module, entry.lowered[i].c_str()) == hipSuccess;
-      if (ok) {
-        if (code_size) *code_size = entry.code.size();
-        {
-          std::lock_guard<std::mutex> lock(g_cache_mutex);
-          g_cache.emplace(cache_key, std::move(entry));
-        }
-        *out = k;
-        return 0;
-      }
-      (void)hipGetLastError();                         // a code object this device does not take: compile afresh, overwrite
-      rtc_release(&k);
+  const std::string disk_path = out ? disk_cache_path(cache_key, rq.csrc_dir) : std::string();
+  CachedModule entry;
+  if (!disk_path.empty() && disk_cache_load(disk_path, (int)table.size(), &entry)) {
+    std::string refused;
+    if (load_kernels(entry, rq, out, &refused)) {
+      if (code_size) *code_size = entry.code.size();
+      std::lock_guard<std::mutex> lock(g_cache_mutex);
+      g_cache.emplace(cache_key, std::move(entry));
+      return 0;
     }
+    (void)hipGetLastError();                           // a code object this device does not take: compile afresh, overwrite
   }
-  void *prog = nullptr;
-  if (api->CreateProgram(&prog, src.c_str(), "sabc_user_simulator.hip", 0, nullptr, nullptr)) { *log = "hiprtcCreateProgram failed"; return -1; }
-  for (int i = 0; i < kKernels; ++i) api->AddNameExpression(prog, name[i]);
+
+  Program prog{api};
+  if (api->CreateProgram(&prog.p, src.c_str(), "sabc_user_simulator.hip", 0, nullptr, nullptr)) { *log = "hiprtcCreateProgram failed"; return -1; }
+  for (const KernelEntry &e : table) api->AddNameExpression(prog.p, e.name.c_str());
   const char *rocm = std::getenv("ROCM_PATH");
   const std::string inc_rocm = std::string("-I") + (rocm && *rocm ? rocm : "/opt/rocm") + "/include";
-  const std::string inc_csrc = "-I" + csrc_dir;
-  // the launch geometry the host library was built with (launch_update, build_coarse) must be the one the kernels are
-  // compiled for: a variant library (tools/build_variants.sh) forwards its -D overrides to the run-time compiler
-#define SABC_RTC_STR2(x) #x
-#define SABC_RTC_STR(x) SABC_RTC_STR2(x)
-  std::vector<const char *> opts = {"--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=fast", inc_csrc.c_str(), inc_rocm.c_str(),
-                        "-DSABC_UPDATE_BLOCK=" SABC_RTC_STR(SABC_UPDATE_BLOCK), "-DSABC_UPDATE_BLOCK_MS=" SABC_RTC_STR(SABC_UPDATE_BLOCK_MS),
-                        "-DSABC_CDF_COARSE=" SABC_RTC_STR(SABC_CDF_COARSE), "-DSABC_CDF_COARSE_MS=" SABC_RTC_STR(SABC_CDF_COARSE_MS),
-                        "-DSABC_UPDATE_MIN_WAVES=" SABC_RTC_STR(SABC_UPDATE_MIN_WAVES),
-                        "-DSABC_UPDATE_MIN_WAVES_MS=" SABC_RTC_STR(SABC_UPDATE_MIN_WAVES_MS)};
-#undef SABC_RTC_STR
-#undef SABC_RTC_STR2
-  if (user_prior) opts.push_back("-DSABC_USER_PRIOR=1");
+  const std::string inc_csrc = "-I" + rq.csrc_dir;
+  std::vector<const char *> opts = {"--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=fast", inc_csrc.c_str(), inc_rocm.c_str()};
+  opts.insert(opts.end(), std::begin(kGeometry), std::end(kGeometry));
+  if (rq.user_prior) opts.push_back("-DSABC_USER_PRIOR=1");
   std::vector<std::string> extra_words;
   for (size_t i = 0; i < extra.size();) {
     while (i < extra.size() && extra[i] == ' ') ++i;
@@ -356,72 +409,39 @@ int rtc_compile(const char *user_source, int d, int s, const std::string &csrc_d
     i = j;
   }
   for (const std::string &w : extra_words) opts.push_back(w.c_str());
-  const int rc = api->CompileProgram(prog, (int)opts.size(), opts.data());
+  const int rc = api->CompileProgram(prog.p, (int)opts.size(), opts.data());
   size_t ls = 0;
-  api->GetProgramLogSize(prog, &ls);
-  if (ls > 1) { log->assign(ls, '\0'); api->GetProgramLog(prog, &(*log)[0]); }
+  api->GetProgramLogSize(prog.p, &ls);
+  if (ls > 1) { log->assign(ls, '\0'); api->GetProgramLog(prog.p, &(*log)[0]); }
   if (rc) {
     if (log->empty()) *log = "hiprtcCompileProgram failed";
-    api->DestroyProgram(&prog);
     return -1;
   }
   size_t cs = 0;
-  api->GetCodeSize(prog, &cs);
+  api->GetCodeSize(prog.p, &cs);
   if (code_size) *code_size = cs;
-  if (!out) {                                         // compile-only check: every kernel must be there by name
-    // $SABC_RTC_CODE_OUT: the code object is also written to that file (its metadata -- registers, LDS, scratch -- can be
-    // read there without a device: tests/test_source_many_stats.py)
-    if (const char *dump = std::getenv("SABC_RTC_CODE_OUT")) {
-      std::vector<char> code(cs);
-      api->GetCode(prog, code.data());
-      FILE *fp = std::fopen(dump, "wb");
-      const bool ok = fp && std::fwrite(code.data(), 1, cs, fp) == cs;
-      if (fp) std::fclose(fp);
-      if (!ok) { *log = std::string("could not write the code object to ") + dump; api->DestroyProgram(&prog); return -1; }
-    }
-    for (int i = 0; i < kKernels; ++i) {
-      const char *lowered = nullptr;
-      if (api->GetLoweredName(prog, name[i], &lowered) || !lowered) {
-        *log = std::string("kernel missing from the compiled module: ") + name[i];
-        api->DestroyProgram(&prog);
-        return -1;
-      }
-    }
-    api->DestroyProgram(&prog);
-    return 0;
+  entry.code.resize(cs);
+  api->GetCode(prog.p, entry.code.data());
+  // $SABC_RTC_CODE_OUT, compile only: the code object is also written to that file (its metadata -- registers, LDS, scratch --
+  // can be read there without a device: tests/test_source_many_stats.py)
+  const char *dump = out ? nullptr : std::getenv("SABC_RTC_CODE_OUT");
+  if (dump) {
+    FILE *fp = std::fopen(dump, "wb");
+    const bool ok = fp && std::fwrite(entry.code.data(), 1, cs, fp) == cs;
+    if (fp) std::fclose(fp);
+    if (!ok) { *log = std::string("could not write the code object to ") + dump; return -1; }
   }
-  std::vector<char> code(cs);
-  api->GetCode(prog, code.data());
-  RtcKernels k;
-  k.d = d; k.s = s;
-  if (hipModuleLoadData(&k.module, code.data()) != hipSuccess) {
-    *log = "hipModuleLoadData of the compiled simulator failed";
-    api->DestroyProgram(&prog);
-    return -1;
-  }
-  hipFunction_t *slots[kMaxKernels] = {&k.prior_simulate, &k.update[0], &k.update[1], &k.update[2], &k.simulate_batch, &k.stats, &k.prior_op,
-                                        &k.persistent[0], &k.persistent[1], &k.persistent[2], &k.persistent4[0], &k.persistent4[1], &k.persistent4[2],
-                                        &k.persistent16[0], &k.persistent16[1], &k.persistent16[2]};
-  CachedModule entry;
-  for (int i = 0; i < kKernels; ++i) {
+  entry.lowered.clear();
+  for (const KernelEntry &e : table) {                 // every kernel must be there by name
     const char *lowered = nullptr;
-    if (api->GetLoweredName(prog, name[i], &lowered) || !lowered ||
-        hipModuleGetFunction(slots[i], k.module, lowered) != hipSuccess) {
-      *log = std::string("kernel not found in the compiled module: ") + name[i];
-      api->DestroyProgram(&prog);
-      rtc_release(&k);
-      return -1;
-    }
-    entry.lowered[i] = lowered;
+    if (api->GetLoweredName(prog.p, e.name.c_str(), &lowered) || !lowered) { *log = "kernel missing from the compiled module: " + e.name; return -1; }
+    entry.lowered.push_back(lowered);
   }
-  api->DestroyProgram(&prog);
-  entry.code = std::move(code);
-  if (!disk_path.empty()) disk_cache_store(disk_path, kKernels, entry);
-  {
-    std::lock_guard<std::mutex> lock(g_cache_mutex);
-    g_cache.emplace(cache_key, std::move(entry));
-  }
-  *out = k;
+  if (!out) return 0;                                  // the compile-only check ends here
+  if (!load_kernels(entry, rq, out, log)) return -1;
+  if (!disk_path.empty()) disk_cache_store(disk_path, entry);
+  std::lock_guard<std::mutex> lock(g_cache_mutex);
+  g_cache.emplace(cache_key, std::move(entry));
   return 0;
 }
 
