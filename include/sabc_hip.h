@@ -228,6 +228,13 @@ SABC_API int64_t     sabc_host_callback_calls(const sabc_handle *h);
    data_at reads through the constant address space: an index that is the same in every lane of a wave costs one scalar load
    per wave, an index that differs per lane a vector load.  Indices are not checked.  A new data set needs no new source and
    no new compilation.
+   OUTPUTS: what a simulation looks like, not only how far from the data it lies.  The source hands values out through
+       bool      sabc::emitting(const sabc::NormalStream &rng);    false in every kernel but a forward run that asked for outputs
+       long long sabc::n_outputs(const sabc::NormalStream &rng);   how many outputs the caller asked for (0 when not emitting)
+       void      sabc::emit(sabc::NormalStream &rng, long long i, double v);      output i of THIS simulation
+   emit does nothing when not emitting and ignores an i outside [0, n_outputs) -- this index IS checked.  An output that is never
+   emitted (a simulation may stop early) reads as NaN.  Population updates never emit: there every emit, and every block under
+   `if (sabc::emitting(rng))`, is dead code the compiler removes.  sabc_op_simulate_outputs below is the forward run.
    It is compiled with hipRTC for gfx950 against csrc/update_kernel.hpp -- the same propose -> simulate -> ECDF -> accept
    kernel, reductions and Philox streams as the built-in simulators -- and must be registered before sabc_initialize.
    On failure sabc_last_error(h) holds the compiler log. */
@@ -371,6 +378,22 @@ SABC_API int sabc_op_eps_multi(const double *ubar, int32_t s, double v, double *
    particle ids pid0..pid0+m-1 at iteration `iter` */
 SABC_API int sabc_op_simulate(sabc_handle *h, const double *theta, int64_t m, uint64_t pid0, uint64_t iter,
                               double *rho_out);
+/* The forward run of a simulator from source: row i of theta (column-major m x d) is simulated as particle pid0 + i at
+   iteration `iter`, on the stream the update of that particle and iteration ran on (SABC_STREAM_UPDATE: the very simulation
+   sabc_op_simulate returns the distances of) or on a stream no update ever uses (SABC_STREAM_PREDICT: what a predictive check
+   draws from -- re-running the update's stream would reproduce simulations that were accepted BECAUSE they lay close to the
+   data).  out [n_out][m] receives what the source handed to sabc::emit, NaN where nothing was emitted; n_out may be smaller
+   than what the source emits (the rest is dropped) or larger.  rho_out [s][m] receives the distances; NULL skips them.  No
+   prior and no gate are consulted and no state of the handle changes (population, control block, counters, histories, data);
+   legal before sabc_initialize.  Device staging belongs to the call and holds at most 128 MB of outputs: a larger call runs
+   in chunks of rows.  n_out = 0 with rho_out set is sabc_op_simulate on the chosen stream.  SABC_ERR_BAD_CONFIG, with the
+   reason in sabc_last_error: n_out < 0, an unknown stream, a handle that is not SABC_MODEL_USER with n_out > 0 or with
+   SABC_STREAM_PREDICT, no registered source. */
+#define SABC_STREAM_UPDATE  0   /* PURPOSE_SIM: the simulation an update ran for (pid, iter) */
+#define SABC_STREAM_PREDICT 1   /* PURPOSE_PREDICT: streams no update ever uses */
+SABC_API int sabc_op_simulate_outputs(sabc_handle *h, const double *theta, int64_t m, uint64_t pid0, uint64_t iter,
+                                      int32_t stream, int32_t n_out, double *rho_out /* [s][m] or NULL */,
+                                      double *out /* [n_out][m] */);
 /* rand(prior) and logpdf(prior, .) on device (SimulatedAnnealingABC.jl:174,314,318) for particle ids pid0..pid0+m-1:
    theta_out column-major m x d, logpdf_out m values (the log density of each draw) */
 SABC_API int sabc_op_prior(sabc_handle *h, uint64_t pid0, int64_t m, double *theta_out, double *logpdf_out);

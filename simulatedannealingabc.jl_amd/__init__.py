@@ -6,8 +6,8 @@ Public surface = the reference's exports (`sabc`, `update_population!` -> `updat
 (hand-written gfx950 HIP kernels behind the C-ABI of include/sabc_hip.h); there is no CPU path.
 """
 from ._lib import SABCError, build, lib  # noqa: F401
-from .api import (SABCresult, SABCstate, initialization, is_logging, load_result, sabc, save_result,  # noqa: F401
-                  update_population_)
+from .api import (SABCresult, SABCstate, initialization, is_logging, load_result, posterior_predictive, sabc,  # noqa: F401
+                  save_result, simulate_outputs, update_population_)
 from .distributions import (Beta, Exponential, Gamma, HostPrior, LogNormal, MvNormal, Normal, Product, SourcePrior,  # noqa: F401
                             TruncatedNormal, Uniform, from_scipy, product_distribution, truncated)
 from .handle import (SabcHandle, op_build_cdf, op_cdf_eval, op_eps_multi, op_eps_single,  # noqa: F401
@@ -17,7 +17,7 @@ from .models import (DeviceDistance, DeviceSource, GandK, Gaussian2D, GaussianII
 from .proposals import DifferentialEvolution, Proposal, RandomWalk, StretchMove  # noqa: F401
 
 __all__ = [
-    "sabc", "update_population_", "initialization", "save_result", "load_result", "SABCresult", "SABCstate", "SABCError",
+    "sabc", "update_population_", "initialization", "save_result", "load_result", "simulate_outputs", "posterior_predictive", "SABCresult", "SABCstate", "SABCError",
     "RandomWalk", "DifferentialEvolution", "StretchMove", "Proposal",
     "Normal", "Uniform", "Exponential", "LogNormal", "Gamma", "Beta", "TruncatedNormal", "truncated", "MvNormal", "HostPrior", "SourcePrior", "from_scipy", "Product", "product_distribution",
     "DeviceDistance", "DeviceSource", "HostDistance", "GaussianIID", "Gaussian2D", "GandK", "LotkaVolterra", "StochasticSIR",

@@ -25,6 +25,7 @@ MODEL_HOST, MODEL_GAUSS_IID, MODEL_GAUSS2D, MODEL_GK, MODEL_LV, MODEL_USER = 0, 
 PRIOR_NORMAL, PRIOR_UNIFORM, PRIOR_EXPONENTIAL, PRIOR_LOGNORMAL, PRIOR_GAMMA, PRIOR_BETA, PRIOR_TRUNCNORMAL = 0, 1, 2, 3, 4, 5, 6
 PROP_RANDOMWALK, PROP_DIFFEVO, PROP_STRETCH = 0, 1, 2
 ALG_SINGLE_EPS, ALG_MULTI_EPS = 0, 1
+STREAM_UPDATE, STREAM_PREDICT = 0, 1     # sabc_op_simulate_outputs: the update's simulation stream | streams no update uses
 KERNEL_UPDATE, KERNEL_REDUCE, KERNEL_RESAMPLE, KERNEL_INIT, KERNEL_COLLECTIVE = 0, 1, 2, 3, 4
 
 ERR_NAMES = {
@@ -179,6 +180,7 @@ def bind(L, strict=True):
         "sabc_op_eps_single": ([C.c_double, C.c_double, dp], C.c_int),
         "sabc_op_eps_multi": ([dp, C.c_int32, C.c_double, dp], C.c_int),
         "sabc_op_simulate": ([vp, dp, C.c_int64, C.c_uint64, C.c_uint64, dp], C.c_int),
+        "sabc_op_simulate_outputs": ([vp, dp, C.c_int64, C.c_uint64, C.c_uint64, C.c_int32, C.c_int32, dp, dp], C.c_int),
         "sabc_op_prior": ([vp, C.c_uint64, C.c_int64, dp, dp], C.c_int),
         "sabc_op_philox": ([C.c_int32, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint32,
                             C.POINTER(C.c_uint32), dp], C.c_int),

@@ -360,6 +360,78 @@ def update_population_(population_state: SABCresult, f_dist, prior, *args, n_sim
     return res
 
 
+def _outputs_model(f_dist):
+    """The model of a forward run, or the TypeError that says why there is none (before any handle is made)."""
+    if isinstance(f_dist, HostDistance) or (not isinstance(f_dist, DeviceDistance) and callable(f_dist)):
+        raise TypeError("the outputs of a host-callable f_dist are already on the host: call it; simulate_outputs / "
+                        "posterior_predictive run a simulator from source (DeviceSource) forward")
+    if getattr(f_dist, "model_id", None) != _lib.MODEL_USER:
+        raise TypeError(f"{type(f_dist).__name__} is a built-in simulator and has nothing to emit: outputs come from a "
+                        "simulator from source (DeviceSource)")
+    if getattr(f_dist, "n_outputs", None) is None:
+        raise TypeError(f"{type(f_dist).__name__} declares no outputs: construct it with n_outputs= (and let its source "
+                        "call sabc::emit)")
+    return f_dist
+
+
+def _theta_rows(theta, d):
+    """theta as [d][m]: m x d, or length m for one parameter."""
+    th = np.asarray(theta, dtype=np.float64)
+    if d == 1 and th.ndim <= 1:
+        th = th.reshape(-1, 1)
+    if th.ndim != 2 or th.shape[1] != d:
+        raise ValueError(f"theta is m x {d}" + (" (or of length m)" if d == 1 else "") + f", got shape {th.shape}")
+    return np.ascontiguousarray(th.T)
+
+
+def simulate_outputs(f_dist, theta, *args, n_rep=1, seed=None, device=None, **kwargs):
+    """Run a simulator from source forward, without a population: what `f_dist` emits (sabc::emit) for every row of `theta`
+    (m x d, or length m for one parameter), `n_rep` times -> array (m, n_rep, n_out), NaN where a simulation emitted nothing.
+    `*args` / `**kwargs` are the data, bound exactly as `sabc` binds them.  Row i, replicate j is particle i at iteration j
+    on the predictive streams of `seed` (random if omitted): streams no population update uses."""
+    model = _outputs_model(f_dist)
+    data = _device_data(model, args, kwargs)
+    if data is None and getattr(model, "data_names", None) and getattr(model, "data", None) is None:
+        raise TypeError(f"{type(model).__name__} has no data: give them at construction or to this call, data_names = {model.data_names!r}")
+    n_out = model.n_outputs_for(data)
+    d = model.n_para[0]
+    th = _theta_rows(theta, d)
+    if int(n_rep) < 1:
+        raise ValueError("n_rep is at least 1")
+    from .distributions import Uniform, product_distribution
+    prior = Uniform(0.0, 1.0) if d == 1 else product_distribution([Uniform(0.0, 1.0)] * d)     # never drawn from
+    h = SabcHandle(n_particles=128, model=model, prior=prior, seed=secrets.randbits(63) if seed is None else seed,
+                   device=0 if device is None else device)
+    try:
+        if data is not None:
+            h.set_data(data)
+        out = np.empty((th.shape[1], int(n_rep), n_out))
+        for j in range(int(n_rep)):
+            out[:, j, :] = h.simulate_outputs(th, 0, j, n_out, stream="predict")[1].T
+    finally:
+        h.close()
+    return out
+
+
+def posterior_predictive(res: SABCresult, n_rep=1, return_distances=False):
+    """Simulations at the particles of a result, next to the data: every particle of `res.population` is run forward `n_rep`
+    times on the result's own handle -- its model and the data it holds now -- and what the source emits comes back as
+    (n, n_rep, n_out); with return_distances=True also the distances (n, n_rep, s).  Replicate j of particle i is iteration j
+    of particle id local_offset + i on the predictive streams, which no update uses: re-running an update's own stream would
+    reproduce the simulations that were accepted because they lay close to the data.  `res` is left untouched."""
+    _outputs_model(res._model)
+    h = res._handle
+    n_out = h.n_outputs
+    if int(n_rep) < 1:
+        raise ValueError("n_rep is at least 1")
+    th = _theta_rows(res.population, h.d)
+    out, rho = np.empty((th.shape[1], int(n_rep), n_out)), np.empty((th.shape[1], int(n_rep), h.s))
+    for j in range(int(n_rep)):
+        r, o = h.simulate_outputs(th, res.local_offset, j, n_out, stream="predict")
+        out[:, j, :], rho[:, j, :] = o.T, r.T
+    return (out, rho) if return_distances else out
+
+
 def save_result(path, res: SABCresult):
     """Serialise a result, ECDF knots included, so that `update_population_` can resume from it in
     another process (the reference only resumes in memory, SimulatedAnnealingABC.jl:264-271)."""

@@ -662,6 +662,16 @@ int sabc_op_simulate(sabc_handle *h, const double *theta, int64_t m, uint64_t pi
   return h->be->simulate_host(theta, m, pid0, iter, rho_out) ? hfail(h, SABC_ERR_HIP) : 0;
 }
 
+int sabc_op_simulate_outputs(sabc_handle *h, const double *theta, int64_t m, uint64_t pid0, uint64_t iter, int32_t stream,
+                             int32_t n_out, double *rho_out, double *out) {
+  if (!h) return SABC_ERR_STATE;
+  if (stream != SABC_STREAM_UPDATE && stream != SABC_STREAM_PREDICT)
+    return hset(h, SABC_ERR_BAD_CONFIG, "sabc_op_simulate_outputs: stream is SABC_STREAM_UPDATE or SABC_STREAM_PREDICT");
+  const int rc = h->be->simulate_outputs_host(theta, m, pid0, iter, stream == SABC_STREAM_PREDICT ? kPurposePredict : kPurposeSim, n_out,
+                                              rho_out, out);
+  return rc ? hfail(h, rc == SABC_ERR_BAD_CONFIG ? SABC_ERR_BAD_CONFIG : SABC_ERR_HIP) : 0;
+}
+
 int sabc_op_prior(sabc_handle *h, uint64_t pid0, int64_t m, double *theta_out, double *logpdf_out) {
   if (!h || !theta_out || !logpdf_out) return SABC_ERR_STATE;
   return h->be->prior_host(pid0, m, theta_out, logpdf_out) ? hfail(h, SABC_ERR_HIP) : 0;

@@ -17,7 +17,8 @@
 namespace sabc {
 
 enum : uint32_t { PURPOSE_PRIOR = 0, PURPOSE_SIM = 1, PURPOSE_PROP = 2, PURPOSE_PROP2 = 3, PURPOSE_ACCEPT = 4,
-                  PURPOSE_RESAMPLE = 5 };
+                  PURPOSE_RESAMPLE = 5,
+                  PURPOSE_PREDICT = 6 };   // forward runs for predictive checks (sabc_op_simulate_outputs): streams no update uses
 
 struct u32x4 { uint32_t x, y, z, w; };
 
@@ -453,9 +454,19 @@ struct NormalStream {
   int buf_block;                 // coop: first block of the group of W this lane holds one block of (-1: none) ...
   bool buf_uniform;              // ... as uniforms (uniform_pair) or as a Box-Muller pair
   double b0, b1;
+  // where sabc::emit puts the outputs of THIS simulation: output i at out[i * out_stride], i < out_n.  Null from every
+  // constructor: only the forward run (Sim<SABC_MODEL_USER>::run_out) sets a destination, so in every other kernel
+  // the null is a constant after inlining and what a simulator does for its outputs is dead code there
+  double *out;
+  long long out_stride, out_n;
   __device__ __forceinline__ NormalStream(uint64_t seed_, uint64_t pid_, uint32_t purpose_, uint64_t iter_, int coop_ = 0)
       : seed(seed_), pid(pid_), iter(iter_), purpose(purpose_), k(0), spare(0.0), have(false), coop(coop_), buf_block(-1),
-        buf_uniform(false), b0(0.0), b1(0.0) {}
+        buf_uniform(false), b0(0.0), b1(0.0), out(nullptr), out_stride(0), out_n(0) {}
+  __device__ __forceinline__ void set_outputs(double *out_, long long stride_, long long n_) {
+    out = out_;
+    out_stride = stride_;
+    out_n = out_ ? n_ : 0;
+  }
   __device__ __forceinline__ void pair(double &z0, double &z1) {  // consumes one whole block
     if (coop == 4) { fetch<4>(k++, false, z0, z1); return; }
     if (coop == 16) { fetch<16>(k++, false, z0, z1); return; }
@@ -706,5 +717,16 @@ struct NormalStream {
     x1 = team_pick<W>(b1, kk);
   }
 };
+
+// ---- outputs of a simulator from source (sabc_op_simulate_outputs).  The stream is the one per-simulation object a
+// simulator has, so it carries the destination.  emitting: false in every kernel but a forward run that asked for outputs --
+// the guard for bookkeeping that exists for the outputs only.  emit: output i of THIS simulation; nothing when not emitting,
+// and nothing for an i outside [0, n_outputs): the index IS checked (unlike data_at's), a stray store would land in another
+// simulation's outputs or behind the buffer.  What is never emitted reads as NaN on the host.
+__device__ __forceinline__ bool emitting(const NormalStream &rng) { return rng.out != nullptr; }
+__device__ __forceinline__ long long n_outputs(const NormalStream &rng) { return rng.out ? rng.out_n : 0; }
+__device__ __forceinline__ void emit(NormalStream &rng, const long long i, const double v) {
+  if (rng.out && i >= 0 && i < rng.out_n) rng.out[i * rng.out_stride] = v;
+}
 
 }  // namespace sabc

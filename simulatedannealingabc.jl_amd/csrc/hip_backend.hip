@@ -796,6 +796,50 @@ int HipBackend::simulate_host(const double *theta, int64_t n, uint64_t pid0, uin
   return rc;
 }
 
+// sabc_op_simulate_outputs: the forward run.  Row i is particle pid0 + i at iteration `iter` on the stream of `purpose`; what the
+// simulator hands to sabc::emit arrives in out [n_out][n], the distances in rho_out [s][n] (either may be null).  No prior, no
+// gate, nothing of the handle's state is read but the model, the module and the data; nothing is written.  Staging is
+// DeviceBuffers of this call (freed on every way out), the outputs' pre-filled with NaN -- all bits set is one --, so that what
+// a simulation never emits reads as NaN.  A launch stages at most kOutputStageBytes of outputs: a larger call is cut into
+// chunks of rows, each copied into its columns of the caller's arrays (rows of the staging are chunk long, the caller's n).
+int HipBackend::simulate_outputs_host(const double *theta, int64_t n, uint64_t pid0, uint64_t iter, uint32_t purpose,
+                                      int32_t n_out, double *rho_out, double *out) {
+  if (n_out < 0) { err_ = "sabc_op_simulate_outputs: n_out must not be negative"; return SABC_ERR_BAD_CONFIG; }
+  if (purpose != kPurposeSim && purpose != kPurposePredict) { err_ = "sabc_op_simulate_outputs: stream is SABC_STREAM_UPDATE or SABC_STREAM_PREDICT"; return SABC_ERR_BAD_CONFIG; }
+  if (m_.model_id != SABC_MODEL_USER && (n_out > 0 || purpose != kPurposeSim)) {
+    err_ = "sabc_op_simulate_outputs: outputs and the predictive streams belong to a simulator from source, the handle was not created with SABC_MODEL_USER";
+    return SABC_ERR_BAD_CONFIG;
+  }
+  if (m_.model_id == SABC_MODEL_USER && !rtc()) { err_ = "sabc_op_simulate_outputs: no device simulator registered (sabc_register_device_simulator)"; return SABC_ERR_BAD_CONFIG; }
+  if (n < 0 || (n > 0 && (!theta || (n_out > 0 && !out)))) { err_ = "sabc_op_simulate_outputs: null argument or negative m"; return SABC_ERR_BAD_CONFIG; }
+  if (n == 0) return 0;
+  constexpr int64_t kOutputStageBytes = (int64_t)128 << 20;
+  int64_t chunk = kOutputStageBytes / ((int64_t)sizeof(double) * (n_out > 0 ? n_out : 1));
+  if (chunk > 256) chunk -= chunk % 256;                   // whole workgroups, aligned rows
+  if (chunk < 1) chunk = 1;
+  if (chunk > n) chunk = n;
+  HB_CHECK(hipSetDevice(device_), "hipSetDevice");
+  DeviceBuffer<double> d_in, d_rho, d_out;
+  HB_CHECK(d_in.alloc((size_t)chunk * m_.d), "hipMalloc");
+  HB_CHECK(d_rho.alloc((size_t)chunk * m_.s), "hipMalloc");
+  if (n_out > 0) HB_CHECK(d_out.alloc((size_t)chunk * n_out), "hipMalloc");
+  int rc = 0;
+  for (int64_t lo = 0; lo < n && !rc; lo += chunk) {
+    const int64_t cnt = n - lo < chunk ? n - lo : chunk;
+    const size_t w = (size_t)cnt * sizeof(double), pitch = (size_t)n * sizeof(double);
+    rc = check(hipMemcpy2DAsync(d_in.get(), w, theta + lo, pitch, w, (size_t)m_.d, hipMemcpyHostToDevice, stream_), "memcpy2D(theta)");
+    if (!rc && n_out > 0) rc = check(hipMemsetAsync(d_out.get(), 0xFF, w * (size_t)n_out, stream_), "memset(outputs)");
+    if (!rc) rc = check((hipError_t)launch_simulate_batch(m_, d_in.get(), cnt, pid0 + (uint64_t)lo, iter, d_rho.get(), stream_, rtc(), nullptr,
+                                                          n_out > 0 ? d_out.get() : nullptr, n_out, purpose), "k_simulate_batch");
+    if (!rc && rho_out) rc = check(hipMemcpy2DAsync(rho_out + lo, pitch, d_rho.get(), w, w, (size_t)m_.s, hipMemcpyDeviceToHost, stream_), "memcpy2D(rho)");
+    if (!rc && n_out > 0) rc = check(hipMemcpy2DAsync(out + lo, pitch, d_out.get(), w, w, (size_t)n_out, hipMemcpyDeviceToHost, stream_), "memcpy2D(outputs)");
+    // (the staging is reused by the next chunk: the copies out of it are complete before it is written again)
+    const int rs = check(hipStreamSynchronize(stream_), "hipStreamSynchronize");
+    if (!rc) rc = rs;
+  }
+  return rc;
+}
+
 // ---- peer-to-peer transport (p2p.hpp) ----------------------------------------------------------
 int64_t HipBackend::parked_bytes() { return g_parked_bytes.load(); }
 

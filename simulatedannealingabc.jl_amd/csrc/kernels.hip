@@ -559,14 +559,17 @@ int launch_cdf_apply_matrix(CdfPtrs cdf, int s, const double *rho, int64_t m, do
   return SABC_LAUNCH_RC();
 }
 
+static_assert(kPurposeSim == PURPOSE_SIM && kPurposePredict == PURPOSE_PREDICT, "kernels.hpp restates device_rng.hpp's purposes");
 int launch_simulate_batch(const ModelDesc &m, const double *theta, int64_t n, uint64_t pid0, uint64_t iter,
-                          double *rho_out, hipStream_t stream, const RtcKernels *rtc, const unsigned char *gate) {
+                          double *rho_out, hipStream_t stream, const RtcKernels *rtc, const unsigned char *gate,
+                          double *out, int64_t n_out, uint32_t purpose) {
   if (n <= 0) return 0;
   if (m.model_id == SABC_MODEL_USER) {
     if (!rtc || !rtc->simulate_batch) return (int)hipErrorInvalidValue;
     return module_launch(rtc->simulate_batch, source_blocks(m, n), source_block(m), stream, nullptr, nullptr, m, theta, n, pid0, iter,
-                         rho_out, gate);
+                         rho_out, gate, out, n_out, purpose);
   }
+  if (out || purpose != PURPOSE_SIM) return (int)hipErrorInvalidValue;      // outputs and other streams: simulators from source only
   if (m.model_id == SABC_MODEL_GK) {                  // (the gate is not looked at: the wave-cooperative simulator is a fixed
                                                       // amount of arithmetic for any theta, and gated-out rows are never read)
     hipLaunchKernelGGL(k_simulate_gk, dim3(gk_blocks(n)), dim3(kBlock), 0, stream, m, theta, n, n, pid0, iter, 0,
@@ -576,7 +579,8 @@ int launch_simulate_batch(const ModelDesc &m, const double *theta, int64_t n, ui
   const dim3 grid((unsigned)n_blocks(n)), block(kBlock);
   const bool known = for_model(m, [&](auto mc) {
     using C = decltype(mc);
-    hipLaunchKernelGGL((k_simulate_batch<C::model, C::d, C::s>), grid, block, 0, stream, m, theta, n, pid0, iter, rho_out, gate);
+    hipLaunchKernelGGL((k_simulate_batch<C::model, C::d, C::s>), grid, block, 0, stream, m, theta, n, pid0, iter, rho_out, gate,
+                       (double *)nullptr, (int64_t)0, (uint32_t)PURPOSE_SIM);
   });
   return known ? SABC_LAUNCH_RC() : (int)hipErrorInvalidValue;
 }

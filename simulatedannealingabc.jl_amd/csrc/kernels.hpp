@@ -250,8 +250,11 @@ int launch_stats_rt(const ModelDesc &m, const ControlBlock *cb, PopPtrs pp, doub
 // operators
 int launch_cdf_eval(const double *knots, int64_t len, const double *q, int64_t m, double *out, hipStream_t stream);
 int launch_cdf_apply_matrix(CdfPtrs cdf, int s, const double *rho, int64_t m, double *u_out, hipStream_t stream);
+// the stream purposes (device_rng.hpp) a host caller of launch_simulate_batch chooses between; kernels.hip holds them to the enum
+constexpr uint32_t kPurposeSim = 1, kPurposePredict = 6;
 int launch_simulate_batch(const ModelDesc &m, const double *theta, int64_t n, uint64_t pid0, uint64_t iter,
-                          double *rho_out, hipStream_t stream, const RtcKernels *rtc = nullptr, const unsigned char *gate = nullptr);
+                          double *rho_out, hipStream_t stream, const RtcKernels *rtc = nullptr, const unsigned char *gate = nullptr,
+                          double *out = nullptr, int64_t n_out = 0, uint32_t purpose = kPurposeSim);   // out [n_out][n]: a simulator from source's sabc::emit
 int launch_prior_op(const ModelDesc &m, uint64_t pid0, int64_t n, double *theta, double *lp, hipStream_t stream,
                     const RtcKernels *rtc = nullptr);
 int launch_normal_pairs(uint64_t seed, uint64_t pid0, uint32_t purpose, uint64_t iter, uint32_t k, int64_t m, double *out,

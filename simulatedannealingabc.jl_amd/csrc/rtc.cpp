@@ -241,6 +241,13 @@ __device__ __forceinline__ double data_at(long long i, int segment = 0) {
   return ((const_ptr)(sabc_data_desc.base + sabc_data_desc.off[segment]))[i];
 }
 }  // namespace sabc
+// The simulator is the body of every kernel's loop over particles: it is inlined wherever it is called, whatever its size.
+// Left to the inliner's cost estimate, a simulator near the threshold becomes a CALL when the estimate moves -- a member more
+// in NormalStream did that to normal_moments.hip: the stream in scratch (192 bytes), 132 instead of 71 registers in k_update --
+// and only then can what depends on the stream's constants (its coop mode; a null destination of sabc::emit) be folded away.
+// The definition in the user's text inherits the attribute from this declaration.
+__device__ __attribute__((always_inline)) void sabc_user_simulate(const double *theta, const double *params,
+                                                                  sabc::NormalStream &rng, double *rho_out);
 )SABC";
 
 // ... and behind it: the simulator the kernel templates of the unit are instantiated with
@@ -251,6 +258,14 @@ struct Sim<SABC_MODEL_USER, D, S> {
   static __device__ __forceinline__ void run(const ModelDesc &m, const double *th, uint64_t pid, uint64_t iter,
                                              double *rho, int coop = 0) {
     NormalStream ns(m.seed, pid, PURPOSE_SIM, iter, coop);
+    ::sabc_user_simulate(th, m.p, ns, rho);
+  }
+  // the forward run (k_simulate_batch with an output buffer): a lane per simulation, the stream of `purpose`, and on it the
+  // destination of sabc::emit -- output i of this simulation at out[i * stride]
+  static __device__ __forceinline__ void run_out(const ModelDesc &m, const double *th, uint64_t pid, uint32_t purpose,
+                                                 uint64_t iter, double *rho, double *out, long long stride, long long n_out) {
+    NormalStream ns(m.seed, pid, purpose, iter, 0);
+    ns.set_outputs(out, stride, n_out);
     ::sabc_user_simulate(th, m.p, ns, rho);
   }
 };
@@ -367,7 +382,7 @@ int rtc_compile(const RtcRequest &rq, RtcKernels *out, std::string *log, size_t 
   const std::string extra = extra_env ? extra_env : "";
   std::string cache_key = std::to_string(rq.d) + "," + std::to_string(rq.s) + (rq.user_prior ? ",P" : "") + (persistent ? ",1L4L16" : "") + "," + extra;
   for (const char *g : kGeometry) cache_key += std::string(",") + g;
-  cache_key += std::string("\n") + kDataPreamble + "\n" + rq.source;
+  cache_key += std::string("\n") + kDataPreamble + "\n" + kUserSimTail + "\n" + rq.source;
 
   if (out) {                                           // this process has compiled it: a failure here is an error
     std::lock_guard<std::mutex> lock(g_cache_mutex);

@@ -370,12 +370,30 @@ k_prior_op_t(const ModelDesc m, const uint64_t pid0, const int64_t n, double *__
   lp[i] = prior_logpdf<D>(m, th);
 }
 
+// One row of k_simulate_batch.  The forward run (sabc_op_simulate_outputs) shares the kernel: a simulator from source with an
+// output buffer, or on another purpose than PURPOSE_SIM, runs through the second entry of its Sim (run_out: the stream carries
+// the destination of sabc::emit, outputs [n_out][n]); every other launch -- out = nullptr, PURPOSE_SIM: sabc_op_simulate, the
+// host-prior path -- and every built-in model takes run as before.
+template <int MODEL, int D, int S>
+__device__ __forceinline__ void simulate_row(const ModelDesc &m, const double *th, const uint64_t pid, const uint64_t iter,
+                                             double *rho, double *out, const int64_t out_stride, const int64_t n_out,
+                                             const uint32_t purpose) {
+  if constexpr (MODEL == SABC_MODEL_USER) {
+    if (out || purpose != PURPOSE_SIM) {
+      Sim<MODEL, D, S>::run_out(m, th, pid, purpose, iter, rho, out, out_stride, n_out);
+      return;
+    }
+  }
+  Sim<MODEL, D, S>::run(m, th, pid, iter, rho);
+}
+
 // gate (optional, one byte per row): 0 = this theta lies outside the prior's support (SimulatedAnnealingABC.jl:314-315): it is
 // not simulated, its distances are written as 0 and never looked at
 template <int MODEL, int D, int S>
 __global__ void __launch_bounds__(kBlock)
 k_simulate_batch(const ModelDesc m, const double *__restrict__ theta, const int64_t n, const uint64_t pid0,
-                 const uint64_t iter, double *__restrict__ rho_out, const unsigned char *__restrict__ gate) {
+                 const uint64_t iter, double *__restrict__ rho_out, const unsigned char *__restrict__ gate,
+                 double *__restrict__ out, const int64_t n_out, const uint32_t purpose) {
   rng_tables_init();
   const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
   if (i >= n) return;
@@ -385,7 +403,7 @@ k_simulate_batch(const ModelDesc m, const double *__restrict__ theta, const int6
   if (!gate || gate[i]) {
 #pragma unroll
     for (int k = 0; k < D; ++k) th[k] = theta[(int64_t)k * n + i];
-    Sim<MODEL, D, S>::run(m, th, pid0 + (uint64_t)i, iter, rho);
+    simulate_row<MODEL, D, S>(m, th, pid0 + (uint64_t)i, iter, rho, out ? out + i : nullptr, n, n_out, purpose);
   }
 #pragma unroll
   for (int j = 0; j < S; ++j) rho_out[(int64_t)j * n + i] = rho[j];
@@ -579,7 +597,8 @@ __global__ void __launch_bounds__(kWideBlock) k_prior_simulate_wide(const ModelD
 template <int MODEL, int D, int S>
 __global__ void __launch_bounds__(kWideBlock)
 k_simulate_batch_wide(const ModelDesc m, const double *__restrict__ theta, const int64_t n, const uint64_t pid0,
-                      const uint64_t iter, double *__restrict__ rho_out, const unsigned char *__restrict__ gate) {
+                      const uint64_t iter, double *__restrict__ rho_out, const unsigned char *__restrict__ gate,
+                      double *__restrict__ out, const int64_t n_out, const uint32_t purpose) {
   rng_tables_init();
   __shared__ double rows[kWideBlock * wide_row<S>()];
   const int64_t i = (int64_t)blockIdx.x * kWideBlock + threadIdx.x;
@@ -590,7 +609,7 @@ k_simulate_batch_wide(const ModelDesc m, const double *__restrict__ theta, const
     double th[D];
 #pragma unroll
     for (int k = 0; k < D; ++k) th[k] = theta[(int64_t)k * n + i];
-    Sim<MODEL, D, S>::run(m, th, pid0 + (uint64_t)i, iter, rho);
+    simulate_row<MODEL, D, S>(m, th, pid0 + (uint64_t)i, iter, rho, out ? out + i : nullptr, n, n_out, purpose);
   }
   for (int j = 0; j < S; ++j) rho_out[(int64_t)j * n + i] = rho[j];
 }

@@ -5,6 +5,7 @@
 // run has at most 2 S0 + I0 events: the loop's bound is exact.
 // SIR_N_STATS (defined in front of this text by the bindings): 3 = the squared differences of final R, peak I and the time of
 // the peak to the observation, one distance each; 1 = their sum.
+// Outputs (sabc::emit, a forward run only): 0 = final R (total_infected), 1 = peak I (peak_infected), 2 = t_peak.
 #ifndef SIR_N_STATS
 #define SIR_N_STATS 3
 #endif
@@ -47,4 +48,7 @@ __device__ void sabc_user_simulate(const double *theta, const double *p, sabc::N
 #else
   rho[0] = d0 * d0 + d1 * d1 + d2 * d2;
 #endif
+  sabc::emit(rng, 0, (double)R);                   // outputs (a forward run only): total_infected, peak_infected, t_peak
+  sabc::emit(rng, 1, (double)peak);
+  sabc::emit(rng, 2, t_peak);
 }

@@ -4,6 +4,7 @@
 // One statistic: the mean over k of |I(t_k) - I_obs[k]|, I(t_k) being the number infected just before the first event later
 // than t_k, and the final number for every t_k no event comes after.  Event j of a simulation is block j of the particle's
 // simulation stream, exactly as in sir.hip; the curve is compared on the fly, nothing of it is stored.
+// Outputs (sabc::emit, a forward run only): output k = I(t_k), one per observation time.
 // The observation index differs from particle to particle: these reads are vector loads (the data sit in L2 after the first).
 __device__ void sabc_user_simulate(const double *theta, const double *p, sabc::NormalStream &rng, double *rho) {
   const double beta = theta[0], gamma = theta[1];
@@ -23,6 +24,7 @@ __device__ void sabc_user_simulate(const double *theta, const double *p, sabc::N
       t += e / total_rate;
       while (k < K && sabc::data_at(k, 0) < t) {     // observation times this event is the first to lie after
         acc += fabs((double)I - sabc::data_at(k, 1));
+        sabc::emit(rng, k, (double)I);
         ++k;
       }
       if (u < infection_rate / total_rate) {
@@ -34,6 +36,9 @@ __device__ void sabc_user_simulate(const double *theta, const double *p, sabc::N
       return t < t_max && I > 0;
     });
   }
-  for (; k < K; ++k) acc += fabs((double)I - sabc::data_at(k, 1));
+  for (; k < K; ++k) {
+    acc += fabs((double)I - sabc::data_at(k, 1));
+    sabc::emit(rng, k, (double)I);
+  }
   rho[0] = acc / (double)K;
 }

@@ -58,6 +58,8 @@ class SabcHandle:
         self._keep = []   # ctypes callbacks must outlive the handle
         self._host_model = self._host_prior = None
         self._validate_data = getattr(model, "validate_data", None)    # a DeviceSource's own requirements of its data
+        self._outputs_for = getattr(model, "n_outputs_for", None)      # ... and how many outputs it emits for given data
+        self._data_segments = None                                     # the segments set_data was last given
         if getattr(model, "model_id", None) == _lib.MODEL_USER:
             rc = self._L.sabc_register_device_simulator(self._h, model.source.encode())
             if rc:
@@ -146,6 +148,7 @@ class SabcHandle:
         flat = np.ascontiguousarray(np.concatenate(segs) if segs else np.zeros(0), dtype=np.float64)
         lens = (C.c_int64 * max(len(segs), 1))(*[len(s) for s in segs])
         self._check(self._L.sabc_set_device_data(self._h, _dp(flat), len(flat), lens, len(segs)))
+        self._data_segments = segs or None
 
     @property
     def data_len(self):
@@ -339,6 +342,30 @@ class SabcHandle:
         out = np.empty((self.s, th.shape[1]))
         self._check(self._L.sabc_op_simulate(self._h, _dp(th), th.shape[1], int(pid0), int(it), _dp(out)))
         return out
+
+    @property
+    def n_outputs(self):
+        """Outputs a simulation of this handle's model emits for the data the handle holds now (DeviceSource(n_outputs=...));
+        TypeError for a model that declares none."""
+        if self._outputs_for is None:
+            raise TypeError("only a simulator from source (DeviceSource) has outputs: this handle's model declares none")
+        return self._outputs_for(self._data_segments)
+
+    def simulate_outputs(self, theta, pid0, it, n_out=None, stream="update"):
+        """The forward run (sabc_op_simulate_outputs): theta [d][m] -> (rho [s][m], out [n_out][m]), row i as particle pid0 + i
+        at iteration `it`.  out[k] is what the source handed to sabc::emit(rng, k, .), NaN where a simulation emitted nothing.
+        stream="update": the stream the update of (pid, it) simulated on -- rho is simulate()'s; "predict": a stream no update
+        uses (predictive checks).  n_out=None: what the model declares for the handle's data.  Nothing of the handle changes."""
+        streams = {"update": _lib.STREAM_UPDATE, "predict": _lib.STREAM_PREDICT}
+        if stream not in streams:
+            raise ValueError(f"stream is 'update' or 'predict', got {stream!r}")
+        n_out = self.n_outputs if n_out is None else int(n_out)
+        th = np.ascontiguousarray(theta, dtype=np.float64).reshape(self.d, -1)
+        m = th.shape[1]
+        rho, out = np.empty((self.s, m)), np.empty((max(n_out, 0), m))
+        self._check(self._L.sabc_op_simulate_outputs(self._h, _dp(th), m, int(pid0), int(it), streams[stream], n_out,
+                                                     _dp(rho), _dp(out)))
+        return rho, out
 
     def prior(self, pid0, m):
         """rand(prior) for particle ids pid0.. and the log density of each draw, on the device: (theta [d][m], logpdf [m])."""

@@ -21,7 +21,7 @@ import Base: show
 
 export sabc, update_population!, RandomWalk, DifferentialEvolution, StretchMove,
        DeviceDistance, GaussianIID, Gaussian2D, GandK, LotkaVolterra, DeviceSource, StochasticSIR, NormalMoments, StochasticSIRSeries, SourcePrior,
-       comm_unique_id
+       comm_unique_id, simulate_outputs, posterior_predictive
 
 const libsabc = get(ENV, "SABC_HIP_LIB", joinpath(@__DIR__, "..", "libsabc_hip.so"))
 
@@ -509,6 +509,65 @@ function refresh!(res::SABCresult, d::Int, s::Int)
     check(h, ccall((:sabc_get_history, libsabc), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}), h, eh, uh, rh))
     st.ϵ_history = [eh[:, k] for k in 1:m]; st.u_history = [uh[:, k] for k in 1:m]; st.ρ_history = [rh[:, k] for k in 1:m]
     res
+end
+
+# ---- outputs of a simulator from source: what its HIP text hands to sabc::emit(rng, i, v) (include/sabc_hip.h, OUTPUTS) ----
+# θ: m x d, column-major == the library's [d][m]; row i runs as particle pid0 + i - 1 at iteration `iter`, on the stream its
+# update simulated on or (predict) on a stream no update uses.  -> (ρ m x s, out m x n_out), NaN where nothing was emitted
+function forward_run(h::Ptr{Cvoid}, θ::Matrix{Float64}, s::Integer, pid0::Integer, iter::Integer, predict::Bool, n_out::Integer)
+    m = size(θ, 1)
+    ρ = Matrix{Float64}(undef, m, s)
+    out = Matrix{Float64}(undef, m, n_out)
+    GC.@preserve θ ρ out check(h, ccall((:sabc_op_simulate_outputs, libsabc), Cint,
+                                        (Ptr{Cvoid}, Ptr{Float64}, Int64, UInt64, UInt64, Int32, Int32, Ptr{Float64}, Ptr{Float64}),
+                                        h, θ, m, pid0, iter, predict ? 1 : 0, n_out, ρ, out))
+    ρ, out
+end
+
+"""
+    simulate_outputs(f_dist::DeviceSource, θ, n_out; n_rep=1, seed, device=0, data...) -> Array (m, n_rep, n_out)
+
+A forward run without a population: what the source of `f_dist` emits for every row of `θ` (m x d), `n_rep` times.  `data...`
+are bound as `sabc` binds them.  Row i, replicate j is particle i - 1 at iteration j - 1 on the predictive streams of `seed`.
+"""
+function simulate_outputs(f_dist::DeviceSource, θ::AbstractMatrix, n_out::Integer; n_rep::Integer=1, seed=rand(UInt64) >> 1,
+                          device=0, data...)
+    segs = bind_data(f_dist, data)
+    segs === nothing || (f_dist = with_data(f_dist, segs))
+    !isempty(f_dist.data_names) && isempty(f_dist.data) &&
+        throw(ArgumentError("the model has no data: give them at construction or to this call, data_names = $(f_dist.data_names)"))
+    size(θ, 2) == f_dist.n_para || throw(ArgumentError("θ is m x $(f_dist.n_para)"))
+    prior = MvNormal(zeros(f_dist.n_para), 1.0)          # the handle wants a prior; a forward run never consults it
+    h = create_handle(f_dist, prior; n_particles=128, algorithm=:single_eps, v=1.0, δ=0.1, seed, device)
+    th = collect(Float64, θ)
+    res = Array{Float64}(undef, size(th, 1), n_rep, n_out)
+    for j in 1:n_rep
+        res[:, j, :] = forward_run(h[], th, f_dist.n_stats, 0, j - 1, true, n_out)[2]
+    end
+    finalize(h)
+    res
+end
+
+"""
+    posterior_predictive(res::SABCresult, n_out; n_rep=1, return_distances=false) -> Array (n, n_rep, n_out)
+
+Simulations at the particles of `res`, on its own handle and therefore the data it holds now; with `return_distances` also
+the distances (n, n_rep, s).  Predictive streams: no update has drawn from them.  `res` is left untouched.
+"""
+function posterior_predictive(res::SABCresult, n_out::Integer; n_rep::Integer=1, return_distances::Bool=false)
+    h = handle_of(res)[]
+    n, s = size(res.ρ)
+    th = eltype(res.population) <: Real ? reshape(collect(Float64, res.population), n, 1) :
+         collect(Float64, transpose(reduce(hcat, res.population)))
+    pid0 = ccall((:sabc_local_offset, libsabc), Int64, (Ptr{Cvoid},), h)
+    out = Array{Float64}(undef, n, n_rep, n_out)
+    dist = Array{Float64}(undef, n, n_rep, s)
+    for j in 1:n_rep
+        ρ, o = forward_run(h, th, s, pid0, j - 1, true, n_out)
+        out[:, j, :] = o
+        dist[:, j, :] = ρ
+    end
+    return_distances ? (out, dist) : out
 end
 
 # Check if a stream is logged (SimulatedAnnealingABC.jl:500)

@@ -180,10 +180,28 @@ class DeviceSource(DeviceDistance):
     `SabcHandle.set_data(...)`, never another source or another compilation.  With `data_names=("y_obs", "t_obs")`, `sabc`,
     `initialization` and `update_population_` take that many extra positional arguments, or keywords of those names, the way
     the reference hands `args...` / `kwargs...` to `f_dist`: they become the segments in the order of `data_names` and replace
-    what the model was constructed with (in `update_population_`: what the handle holds; data not given leave it)."""
+    what the model was constructed with (in `update_population_`: what the handle holds; data not given leave it).
+
+    Outputs -- what a simulation looks like, not only its distance: the source hands values out with
+    `sabc::emit(rng, i, v)` (output i of this simulation; `sabc::emitting(rng)` and `sabc::n_outputs(rng)` tell whether and how
+    many).  Population updates never emit -- the calls are dead code there --; `simulate_outputs`, `posterior_predictive` and
+    `SabcHandle.simulate_outputs` run the source forward and return what it emitted, NaN where it emitted nothing.  `n_outputs`
+    declares how many there are: an int, or a callable of the data segments (a series model emits one value per observation
+    time); None: the model declares no outputs.  `output_names` names them (then n_outputs may be left out)."""
     model_id = _lib.MODEL_USER
 
-    def __init__(self, hip_source: str, n_para: int, n_stats: int, params=(), data=None, data_names=None):
+    def __init__(self, hip_source: str, n_para: int, n_stats: int, params=(), data=None, data_names=None, n_outputs=None,
+                 output_names=None):
+        self.output_names = None if output_names is None else tuple(str(x) for x in output_names)
+        if n_outputs is None and self.output_names is not None:
+            n_outputs = len(self.output_names)
+        if n_outputs is not None and not callable(n_outputs):
+            if isinstance(n_outputs, bool) or int(n_outputs) != n_outputs or int(n_outputs) < 0:
+                raise ValueError(f"n_outputs is a non-negative integer or a callable of the data segments, got {n_outputs!r}")
+            n_outputs = int(n_outputs)
+            if self.output_names is not None and len(self.output_names) != n_outputs:
+                raise ValueError(f"output_names = {self.output_names!r} names {len(self.output_names)} outputs, n_outputs = {n_outputs}")
+        self.n_outputs = n_outputs
         self.source = str(hip_source)
         self.n_para = (int(n_para),)
         self.n_stats = int(n_stats)
@@ -203,6 +221,24 @@ class DeviceSource(DeviceDistance):
         """What this model's source requires of its data (the source itself checks no index): called wherever data enter --
         the constructor, the extra arguments of sabc / initialization / update_population_, and SabcHandle.set_data of a handle
         made for this model.  Raises ValueError.  The base class accepts anything; the shipped models override it."""
+
+    def n_outputs_for(self, segments=None):
+        """How many outputs a simulation emits for these data segments (None: the data the model was constructed with).
+        TypeError if the model declares no outputs."""
+        if self.n_outputs is None:
+            raise TypeError(f"{type(self).__name__} declares no outputs: construct it with n_outputs= (and let its source "
+                            "call sabc::emit)")
+        if not callable(self.n_outputs):
+            return self.n_outputs
+        segments = self.data if segments is None else segments
+        if segments is None:
+            raise TypeError(f"{type(self).__name__} has no data, and its number of outputs depends on them")
+        n = self.n_outputs(segments)
+        if isinstance(n, bool) or int(n) != n or int(n) < 0:
+            raise ValueError(f"n_outputs(data) must be a non-negative integer, got {n!r}")
+        if self.output_names is not None and len(self.output_names) != int(n):
+            raise ValueError(f"output_names = {self.output_names!r} names {len(self.output_names)} outputs, n_outputs(data) = {n}")
+        return int(n)
 
     def bind_data(self, args, kwargs):
         """The extra arguments of sabc / initialization / update_population_ as data segments in the order of `data_names`;
@@ -258,7 +294,8 @@ class StochasticSIR(DeviceSource):
     Gillespie's direct method, theta = (beta, gamma), started at (S0, I0, R0) and run while t < t_max and I > 0.
     `data_obs` = (total_infected, peak_infected, t_peak) -- a sequence, or a mapping with those keys --; rho = the three squared
     differences to it (n_stats=3, `f_dist_multi_stats`) or their sum (n_stats=1, `f_dist_single_stat`).  The model is the HIP
-    source device_sources/sir.hip, compiled like any `DeviceSource`; `examples.sir_observation` simulates an observation."""
+    source device_sources/sir.hip, compiled like any `DeviceSource`; `StochasticSIR.observe` simulates an observation with it (`examples.sir_observation`: on the
+    host, with NumPy).  Outputs: (total_infected, peak_infected, t_peak)."""
 
     def __init__(self, data_obs, S0=99, I0=1, R0=0, t_max=160.0, n_stats=3):
         comp = []
@@ -278,7 +315,16 @@ class StochasticSIR(DeviceSource):
         self.S0, self.I0, self.R0 = comp
         self.t_max, self.data_obs = float(t_max), tuple(obs)
         super().__init__(f"#define SIR_N_STATS {int(n_stats)}\n" + device_source_text("sir"), 2, int(n_stats),
-                         [*comp, self.t_max, *obs])
+                         [*comp, self.t_max, *obs], output_names=("total_infected", "peak_infected", "t_peak"))
+
+    @classmethod
+    def observe(cls, theta=(0.3, 0.1), S0=99, I0=1, R0=0, t_max=160.0, seed=None, device=None):
+        """An observation made by the device source itself: one forward run at theta = (beta, gamma) on the predictive stream
+        of particle 0, iteration 0 of `seed`, as the dict `examples.sir_observation` returns."""
+        from .api import simulate_outputs
+        model = cls((0.0, 0.0, 0.0), S0=S0, I0=I0, R0=R0, t_max=t_max)
+        out = simulate_outputs(model, np.asarray(theta, dtype=np.float64).reshape(1, 2), seed=seed, device=device)[0, 0]
+        return {name: float(v) for name, v in zip(model.output_names, out)}
 
 
 class NormalMoments(DeviceSource):
@@ -289,7 +335,15 @@ class NormalMoments(DeviceSource):
 
     def __init__(self, y_obs=None, data_names=("y_obs",)):
         super().__init__(device_source_text("normal_moments"), 2, 2, (), data=None if y_obs is None else [_segment(y_obs)],
-                         data_names=data_names)
+                         data_names=data_names, n_outputs=lambda segments: len(segments[0]))      # y_sim, one per observation
+
+    @classmethod
+    def observe(cls, theta, n, seed=None, device=None):
+        """A sample y of n draws of Normal(theta[0], theta[1]) made by the device source itself (the predictive stream of
+        particle 0, iteration 0 of `seed`)."""
+        from .api import simulate_outputs
+        model = cls(y_obs=np.zeros(int(n)))
+        return simulate_outputs(model, np.asarray(theta, dtype=np.float64).reshape(1, 2), seed=seed, device=device)[0, 0]
 
     def validate_data(self, segments):
         if len(segments) != 1 or len(segments[0]) < 1:
@@ -317,7 +371,19 @@ class StochasticSIRSeries(DeviceSource):
             data = [_segment(t_obs), _segment(I_obs)]
         self.S0, self.I0, self.R0 = comp
         self.t_max = float(t_max)
-        super().__init__(device_source_text("sir_series"), 2, 1, [*comp, self.t_max], data=data, data_names=data_names)
+        super().__init__(device_source_text("sir_series"), 2, 1, [*comp, self.t_max], data=data, data_names=data_names,
+                         n_outputs=lambda segments: len(segments[0]))                             # I(t_k), one per observation time
+
+    @classmethod
+    def observe(cls, theta, t_obs=None, S0=99, I0=1, R0=0, t_max=160.0, seed=None, device=None):
+        """An observation made by the device source itself: one forward run at theta = (beta, gamma), observed at the
+        increasing times `t_obs` (default 0, 5, ..., 155), on the predictive stream of particle 0, iteration 0 of `seed`.
+        Returns (t_obs, I_obs) like `examples.sir_series_observation`."""
+        from .api import simulate_outputs
+        t_obs = np.arange(0.0, 160.0, 5.0) if t_obs is None else _segment(t_obs)
+        model = cls(t_obs, np.zeros(len(t_obs)), S0=S0, I0=I0, R0=R0, t_max=t_max)
+        out = simulate_outputs(model, np.asarray(theta, dtype=np.float64).reshape(1, 2), seed=seed, device=device)
+        return t_obs, out[0, 0]
 
     def validate_data(self, segments):
         # the source reads I_obs[k] for every k < len(t_obs): a shorter I_obs would be read past its end on the device
