@@ -1,5 +1,6 @@
-// capi.hip -- the extern "C" surface of libsabc_hip.so (include/sabc_hip.h).
-// Plain pointers and sizes only; no exceptions cross this boundary.
+// capi.hip -- the extern "C" surface of libsabc_hip.so (include/sabc_hip.h): what needs HIP, RCCL or HipBackend's own
+// extras.  The backend-independent half (handle, errors, hook collectives, engine entry points, peer-to-peer set-up) is
+// capi_shared.hpp, included below.  Plain pointers and sizes only; no exceptions cross this boundary.
 #include <hip/hip_runtime.h>
 #include <dlfcn.h>
 
@@ -16,72 +17,13 @@
 #include "hip_backend.hpp"
 #include "host_math.hpp"
 #include "kernels.hpp"
-#include "p2p.hpp"
-#include "p2p_setup.hpp"
 #include "rtc.hpp"
 
-using namespace sabc;
+using CapiBackend = sabc::HipBackend;
+static bool capi_make_current(CapiBackend *be) { return hipSetDevice(be->device()) == hipSuccess; }
+#include "capi_shared.hpp"
 
 namespace {
-
-thread_local std::string g_err;
-
-// world == 1
-class NoCollectives : public Collectives {
- public:
-  // only ever called with world > 1 (the engine skips collectives on one shard): no transport was installed
-  int allreduce_sum(double *, int64_t) override { return -1; }
-  int allgather(const double *, double *, int64_t) override { return -1; }
-  bool usable() const override { return false; }
-};
-
-// user-supplied hooks (torch.distributed from Python, MPI/RCCL from Julia)
-class CallbackCollectives : public Collectives {
- public:
-  CallbackCollectives(HipBackend *be, int world, sabc_allreduce_fn ar, sabc_allgather_fn ag, void *ctx, bool dev)
-      : be_(be), world_(world), ar_(ar), ag_(ag), ctx_(ctx), dev_(dev) {}
-  void set_alltoallv(sabc_alltoallv_fn fn) { a2a_ = fn; }
-  bool has_alltoallv() const override { return a2a_ != nullptr; }
-  int alltoallv(const double *send, const int64_t *sc, double *recv, const int64_t *rc) override {
-    if (!a2a_) return -1;
-    if (dev_) return a2a_(ctx_, send, sc, recv, rc, world_, (void *)be_->stream());
-    int64_t ns = 0, nr = 0;
-    for (int p = 0; p < world_; ++p) { ns += sc[p]; nr += rc[p]; }
-    double *h = be_->host_stage(ns + nr + 2);
-    if (ns > 0 && hipMemcpyAsync(h, send, (size_t)ns * sizeof(double), hipMemcpyDeviceToHost, be_->stream()) != hipSuccess) return -1;
-    if (hipStreamSynchronize(be_->stream()) != hipSuccess) return -1;
-    if (a2a_(ctx_, h, sc, h + ns, rc, world_, nullptr)) return -1;
-    if (nr > 0 && hipMemcpyAsync(recv, h + ns, (size_t)nr * sizeof(double), hipMemcpyHostToDevice, be_->stream()) != hipSuccess) return -1;
-    return hipStreamSynchronize(be_->stream()) == hipSuccess ? 0 : -1;
-  }
-  int allreduce_sum(double *buf, int64_t count) override {
-    if (dev_) return ar_(ctx_, buf, count, (void *)be_->stream());
-    double *h = be_->host_stage(count);
-    if (hipMemcpyAsync(h, buf, (size_t)count * sizeof(double), hipMemcpyDeviceToHost, be_->stream()) != hipSuccess) return -1;
-    if (hipStreamSynchronize(be_->stream()) != hipSuccess) return -1;
-    if (ar_(ctx_, h, count, nullptr)) return -1;
-    if (hipMemcpyAsync(buf, h, (size_t)count * sizeof(double), hipMemcpyHostToDevice, be_->stream()) != hipSuccess) return -1;
-    return hipStreamSynchronize(be_->stream()) == hipSuccess ? 0 : -1;
-  }
-  int allgather(const double *send, double *recv, int64_t count) override {
-    if (dev_) return ag_(ctx_, send, recv, count, (void *)be_->stream());
-    double *h = be_->host_stage(count * (world_ + 1));
-    if (hipMemcpyAsync(h, send, (size_t)count * sizeof(double), hipMemcpyDeviceToHost, be_->stream()) != hipSuccess) return -1;
-    if (hipStreamSynchronize(be_->stream()) != hipSuccess) return -1;
-    if (ag_(ctx_, h, h + count, count, nullptr)) return -1;
-    if (hipMemcpyAsync(recv, h + count, (size_t)count * world_ * sizeof(double), hipMemcpyHostToDevice, be_->stream()) != hipSuccess) return -1;
-    return hipStreamSynchronize(be_->stream()) == hipSuccess ? 0 : -1;
-  }
-
- private:
-  HipBackend *be_;
-  int world_;
-  sabc_allreduce_fn ar_;
-  sabc_allgather_fn ag_;
-  sabc_alltoallv_fn a2a_ = nullptr;
-  void *ctx_;
-  bool dev_;
-};
 
 // RCCL over xGMI, bound at run time so that the library loads on hosts without librccl
 // (and picks up the copy torch already mapped when there is one).
@@ -165,48 +107,35 @@ class RcclCollectives : public Collectives {
   int world_;
 };
 
-int usable_device(int device, std::string &why) {
+// 0, or SABC_ERR_NO_DEVICE with the reason in the global error
+int usable_device(int device) {
   (void)hipGetLastError();   // sticky: do not let an earlier failure leak into the launch checks below
   int n = 0;
   const hipError_t e = hipGetDeviceCount(&n);
   if (e != hipSuccess || n <= 0) {
-    why = "no usable HIP device (libsabc_hip.so has no CPU path): ";
-    why += hipGetErrorString(e);
+    g_err = "no usable HIP device (libsabc_hip.so has no CPU path): ";
+    g_err += hipGetErrorString(e);
     return SABC_ERR_NO_DEVICE;
   }
   if (device < 0 || device >= n) {
-    why = "device ordinal out of range";
+    g_err = "device ordinal out of range";
     return SABC_ERR_NO_DEVICE;
   }
   return 0;
 }
 
-}  // namespace
-
-struct sabc_handle {
-  Engine *eng = nullptr;
-  HipBackend *be = nullptr;
-  Collectives *coll = nullptr;
-  std::string err;
-};
-
-namespace {
-int hfail(sabc_handle *h, int code) {
-  if (!h) return code;
-  h->err = h->eng && !h->eng->error().empty() ? h->eng->error() : h->err;
-  if (h->be && !h->be->error().empty()) { h->err += h->err.empty() ? "" : " | "; h->err += h->be->error(); }
-  return code;
+// The opening of the stand-alone operators: a usable device, the operator's own argument check (bad_args: what is wrong
+// with them, null when nothing is), the device made current.  0, or the code to return with the text in the global error.
+int op_open(int32_t device, const char *bad_args = nullptr, int bad_rc = SABC_ERR_BAD_CONFIG) {
+  if (int rc = usable_device(device)) return rc;
+  if (bad_args) { g_err = bad_args; return bad_rc; }
+  if (hipSetDevice(device) != hipSuccess) { g_err = "hipSetDevice failed"; return SABC_ERR_HIP; }
+  return 0;
 }
-int hset(sabc_handle *h, int code, const char *msg) {
-  if (h) h->err = msg;
-  return code;
-}
+
 }  // namespace
 
 extern "C" {
-
-int sabc_abi_version(void) { return SABC_ABI_VERSION; }
-const char *sabc_last_global_error(void) { return g_err.c_str(); }
 
 int sabc_device_count(void) {
   int n = 0;
@@ -225,9 +154,8 @@ int sabc_create(const sabc_config *cfg, sabc_handle **out) {
   h->eng = new Engine(*cfg, h->be, h->coll);
   int rc = h->eng->validate();
   if (rc) { g_err = h->eng->error(); sabc_destroy(h); return rc; }
-  std::string why;
-  rc = usable_device(cfg->device, why);
-  if (rc) { g_err = why; sabc_destroy(h); return rc; }
+  rc = usable_device(cfg->device);
+  if (rc) { sabc_destroy(h); return rc; }
   if (h->be->allocate(h->eng->model(), h->eng->shard())) {
     g_err = h->be->error();
     sabc_destroy(h);
@@ -245,31 +173,10 @@ void sabc_destroy(sabc_handle *h) {
   delete h;
 }
 
-const char *sabc_last_error(const sabc_handle *h) { return h ? h->err.c_str() : g_err.c_str(); }
-
 int sabc_set_stream(sabc_handle *h, void *hip_stream) {
   if (!h) return SABC_ERR_STATE;
   return h->be->set_stream((hipStream_t)hip_stream) ? hfail(h, SABC_ERR_HIP) : 0;
 }
-
-int sabc_set_collectives(sabc_handle *h, sabc_allreduce_fn ar, sabc_allgather_fn ag, void *ctx, int device_buffers) {
-  if (!h || !ar || !ag) return hset(h, SABC_ERR_COMM, "null collective hook");
-  Collectives *c = new CallbackCollectives(h->be, h->eng->shard().world, ar, ag, ctx, device_buffers != 0);
-  delete h->coll;
-  h->coll = c;
-  h->eng->set_collectives(c);
-  return 0;
-}
-
-int sabc_set_alltoallv(sabc_handle *h, sabc_alltoallv_fn fn) {
-  if (!h || !fn) return hset(h, SABC_ERR_COMM, "null collective hook");
-  CallbackCollectives *c = dynamic_cast<CallbackCollectives *>(h->coll);
-  if (!c) return hset(h, SABC_ERR_COMM, "sabc_set_alltoallv needs the hooks of sabc_set_collectives to be installed first");
-  c->set_alltoallv(fn);
-  return 0;
-}
-
-int64_t sabc_comm_bytes(const sabc_handle *h) { return h ? h->eng->comm_bytes() : 0; }
 
 static int compile_only(const char *hip_source, int32_t d, int32_t s, char *log_out, int64_t log_cap, bool user_prior);
 
@@ -294,12 +201,13 @@ static int compile_only(const char *hip_source, int32_t d, int32_t s, char *log_
 int sabc_register_device_simulator(sabc_handle *h, const char *hip_source) {
   if (!h || !hip_source) return hset(h, SABC_ERR_BAD_CONFIG, "null device simulator source");
   if (h->eng->model().model_id != SABC_MODEL_USER) return hset(h, SABC_ERR_BAD_CONFIG, "the handle was not created with SABC_MODEL_USER");
+  if (int rc = enter(h)) return rc;
   h->err.clear();
   return h->be->register_device_simulator(hip_source) ? hfail(h, SABC_ERR_BAD_CONFIG) : 0;
 }
 
 int sabc_set_device_data(sabc_handle *h, const double *values, int64_t n, const int64_t *segment_len, int32_t n_segments) {
-  if (!h) return SABC_ERR_STATE;
+  if (int rc = enter(h)) return rc;
   h->err.clear();
   const int rc = h->be->set_device_data(values, n, segment_len, n_segments);
   return rc ? hfail(h, rc) : 0;
@@ -338,7 +246,7 @@ int sabc_comm_init_rccl(sabc_handle *h, const void *unique_id_128b) {
   if (!h) return SABC_ERR_STATE;
   RcclApi *a = rccl_api();
   if (!a) return hset(h, SABC_ERR_COMM, "librccl.so could not be loaded");
-  if (hipSetDevice(h->be->device()) != hipSuccess) return hset(h, SABC_ERR_HIP, "hipSetDevice failed");
+  if (int rc = enter(h)) return rc;
   Id128 id;
   std::memcpy(id.b, unique_id_128b, 128);
   void *comm = nullptr;
@@ -350,236 +258,23 @@ int sabc_comm_init_rccl(sabc_handle *h, const void *unique_id_128b) {
   return 0;
 }
 
-// Exercise the installed collectives once and check the result on the host: an allgather of an odd-sized block (5
-// doubles: not a multiple of any vector width), an allreduce, and -- when the transport has one -- a personalised
-// exchange with a different segment length for every (sender, receiver) pair, as the resample issues it.
-// Validates the transport before the first population update.
-int sabc_comm_selftest(sabc_handle *h) {
-  if (!h) return SABC_ERR_STATE;
-  const Shard &sh = h->eng->shard();
-  if (hipSetDevice(h->be->device()) != hipSuccess) return hset(h, SABC_ERR_HIP, "hipSetDevice failed");
-  const int world = sh.world, B = 5;
-  if (world == 1) return 0;
-  double *g = h->be->gather_buffer((int64_t)(world + 1) * B);
-  if (!g) return hset(h, SABC_ERR_HIP, "out of memory for the self-test buffer");
-  double send[B] = {(double)(sh.rank + 1), 2.0, 3.0, (double)(100 + sh.rank), -1.5};
-  std::vector<double> back((size_t)(world + 1) * B, 0.0);
-  if (h->be->to_backend(g, send, B)) return hfail(h, SABC_ERR_HIP);
-  if (h->coll->allgather(g, g + B, B)) return hset(h, SABC_ERR_COMM, "self-test allgather failed");
-  if (h->coll->allreduce_sum(g, B)) return hset(h, SABC_ERR_COMM, "self-test allreduce failed");
-  if (h->be->to_host(back.data(), g, (int64_t)back.size())) return hfail(h, SABC_ERR_HIP);
-  if (back[0] != 0.5 * world * (world + 1) || back[1] != 2.0 * world || back[4] != -1.5 * world)
-    return hset(h, SABC_ERR_COMM, "self-test allreduce gave a wrong sum");
-  for (int r = 0; r < world; ++r)
-    if (back[B + B * r] != (double)(r + 1) || back[B + B * r + 3] != (double)(100 + r) || back[B + B * r + 4] != -1.5)
-      return hset(h, SABC_ERR_COMM, "self-test allgather gave wrong words");
-  if (h->coll->has_alltoallv()) {
-    // rank r sends (r + p + 1) doubles of value 1000 r + p to rank p
-    std::vector<int64_t> sc((size_t)world), rc((size_t)world);
-    int64_t ns = 0, nr = 0;
-    for (int p = 0; p < world; ++p) { sc[(size_t)p] = rc[(size_t)p] = sh.rank + p + 1; ns += sc[(size_t)p]; nr += rc[(size_t)p]; }
-    std::vector<double> out((size_t)ns), in((size_t)nr, 0.0);
-    int64_t o = 0;
-    for (int p = 0; p < world; ++p)
-      for (int64_t k = 0; k < sc[(size_t)p]; ++k) out[(size_t)o++] = 1000.0 * sh.rank + p;
-    double *ds = h->be->scratch_buffer(0, ns), *dr = h->be->scratch_buffer(1, nr);
-    if (!ds || !dr) return hset(h, SABC_ERR_HIP, "out of memory for the self-test buffer");
-    if (h->be->to_backend(ds, out.data(), ns)) return hfail(h, SABC_ERR_HIP);
-    if (h->coll->alltoallv(ds, sc.data(), dr, rc.data())) return hset(h, SABC_ERR_COMM, "self-test alltoallv failed");
-    if (h->be->to_host(in.data(), dr, nr)) return hfail(h, SABC_ERR_HIP);
-    o = 0;
-    for (int p = 0; p < world; ++p)
-      for (int64_t k = 0; k < rc[(size_t)p]; ++k)
-        if (in[(size_t)o++] != 1000.0 * p + sh.rank) return hset(h, SABC_ERR_COMM, "self-test alltoallv gave wrong words");
-  }
-  return 0;
-}
-
-// ---- peer-to-peer transport (csrc/p2p.hpp) ----
-int sabc_comm_p2p_descriptor(sabc_handle *h, void *out_desc) {
-  if (!h || !out_desc) return SABC_ERR_STATE;
-  return h->be->p2p_descriptor(reinterpret_cast<P2PDesc *>(out_desc)) ? hfail(h, SABC_ERR_COMM) : 0;
-}
-
-int sabc_comm_p2p_init(sabc_handle *h, const void *all_descs) {
-  if (!h) return SABC_ERR_STATE;
-  const Shard &sh = h->eng->shard();
-  if (sh.world < 2 || sh.world > SABC_P2P_MAX_WORLD) return hset(h, SABC_ERR_COMM, "the peer-to-peer transport takes 2..8 shards (one node)");
-  if (hipSetDevice(h->be->device()) != hipSuccess) return hset(h, SABC_ERR_HIP, "hipSetDevice failed");
-  std::vector<P2PDesc> all((size_t)sh.world);
-  if (all_descs) {
-    std::memcpy(all.data(), all_descs, all.size() * sizeof(P2PDesc));
-  } else {
-    P2PDesc mine;
-    if (h->be->p2p_descriptor(&mine)) return hfail(h, SABC_ERR_COMM);
-    std::string why;
-    if (int rc = p2p_gather_descriptors(h->be, h->coll, sh.world, mine, all, &why)) return hset(h, rc, why.c_str());
-  }
-  return h->be->p2p_init(all.data()) ? hfail(h, SABC_ERR_COMM) : 0;
-}
-
-// The whole set-up, with the shards agreeing after every step (csrc/p2p_setup.hpp).
-int sabc_comm_p2p_setup(sabc_handle *h) {
-  if (!h) return SABC_ERR_STATE;
-  if (hipSetDevice(h->be->device()) != hipSuccess) return hset(h, SABC_ERR_HIP, "hipSetDevice failed");
-  std::string note;
-  const int rc = p2p_setup_sequence(h->be, h->coll, h->eng->shard(), h->eng->host_mode(), &note);
-  h->err = note;
-  return rc == 1 ? (h->eng->p2p() ? 1 : 0) : rc;
-}
-
-int sabc_comm_p2p_selftest(sabc_handle *h) {
-  if (!h) return SABC_ERR_STATE;
-  return h->be->p2p_selftest() ? hfail(h, SABC_ERR_COMM) : 0;
-}
-
-int sabc_comm_p2p_set_timeout(sabc_handle *h, double milliseconds) {
-  if (!h || !(milliseconds > 0)) return hset(h, SABC_ERR_BAD_CONFIG, "the bound of a peer-to-peer wait must be positive");
-  h->be->p2p_set_timeout(milliseconds);
-  return 0;
-}
-
-int sabc_comm_p2p_disable(sabc_handle *h) {
-  if (!h) return SABC_ERR_STATE;
-  h->be->p2p_disable();
-  return 0;
-}
-
-int sabc_comm_p2p_active(const sabc_handle *h) { return h && h->eng->p2p() ? 1 : 0; }
-int64_t sabc_comm_p2p_fallbacks(const sabc_handle *h) { return h ? h->eng->p2p_fallbacks() : 0; }
-
-int sabc_comm_p2p_inject_silence(sabc_handle *h, int32_t n) {
-  if (!h) return SABC_ERR_STATE;
-  h->be->p2p_inject_silence(n);
-  return 0;
-}
-
-int sabc_comm_p2p_inject_loss(sabc_handle *h, int32_t n) {
-  if (!h) return SABC_ERR_STATE;
-  h->be->p2p_inject_loss(n);
-  return 0;
-}
-
-int sabc_comm_p2p_inject_stale(sabc_handle *h, int32_t n) {
-  if (!h) return SABC_ERR_STATE;
-  h->be->p2p_inject_stale(n);
-  return 0;
-}
-
-int sabc_comm_p2p_set_destroy_wait(sabc_handle *h, double milliseconds) {
-  if (!h || !(milliseconds >= 0)) return hset(h, SABC_ERR_BAD_CONFIG, "the wait of sabc_destroy must not be negative");
-  h->be->p2p_set_destroy_wait(milliseconds);
-  return 0;
-}
-
 int64_t sabc_comm_p2p_parked_bytes(void) { return HipBackend::parked_bytes(); }
 // device and pinned bytes that DeviceBuffer / MappedHostBuffer own right now (device_buffer.hpp); parked memory is not among them
 __attribute__((visibility("default"))) int sabc_debug_live_bytes(int64_t out[2]) {
   out[0] = g_live_bytes[0].load(); out[1] = g_live_bytes[1].load();
   return 0;
 }
-int64_t sabc_persistent_launches(const sabc_handle *h) { return h ? h->eng->persistent_launches() : 0; }
-int32_t sabc_persistent_lanes(const sabc_handle *h) { return h ? h->eng->persistent_lanes() : 0; }
-int64_t sabc_persistent_fallbacks(const sabc_handle *h) { return h ? h->eng->persistent_fallbacks() : 0; }
 
-int sabc_initialize(sabc_handle *h, int64_t n_simulation) {
-  if (!h) return SABC_ERR_STATE;
-  if (hipSetDevice(h->be->device()) != hipSuccess) return hset(h, SABC_ERR_HIP, "hipSetDevice failed");
-  const int rc = h->eng->initialize(n_simulation);
-  return rc ? hfail(h, rc) : 0;
-}
-
-int sabc_update(sabc_handle *h, const sabc_update_args *args) {
-  if (!h || !args) return SABC_ERR_STATE;
-  if (hipSetDevice(h->be->device()) != hipSuccess) return hset(h, SABC_ERR_HIP, "hipSetDevice failed");
-  const int rc = h->eng->update(*args);
-  return rc ? hfail(h, rc) : 0;
-}
-
-int64_t sabc_n_global(const sabc_handle *h) { return h ? h->eng->shard().n_global : 0; }
-int64_t sabc_n_local(const sabc_handle *h) { return h ? h->eng->shard().n_local : 0; }
-int64_t sabc_local_offset(const sabc_handle *h) { return h ? h->eng->shard().gid0 : 0; }
-
-int sabc_get_population(sabc_handle *h, double *theta, double *u, double *rho) {
-  if (!h) return SABC_ERR_STATE;
-  return h->be->download(theta, u, rho) ? hfail(h, SABC_ERR_HIP) : 0;
-}
-
-int sabc_set_population(sabc_handle *h, const double *theta, const double *u, const double *rho) {
-  if (!h) return SABC_ERR_STATE;
-  if (h->be->upload(theta, u, rho)) return hfail(h, SABC_ERR_HIP);
-  h->eng->mark_initialized();
-  return 0;
-}
-
-int sabc_get_counters(const sabc_handle *h, int64_t out[4]) {
-  if (!h) return SABC_ERR_STATE;
-  h->eng->counters(out);
-  return 0;
-}
-int sabc_set_counters(sabc_handle *h, const int64_t in[4]) {
-  if (!h) return SABC_ERR_STATE;
-  h->eng->set_counters(in);
-  return 0;
-}
-int sabc_get_epsilon(const sabc_handle *h, double *eps, int32_t *len) {
-  if (!h) return SABC_ERR_STATE;
-  for (int i = 0; i < h->eng->eps_len(); ++i) eps[i] = h->eng->eps()[i];
-  if (len) *len = h->eng->eps_len();
-  return 0;
-}
-int sabc_set_epsilon(sabc_handle *h, const double *eps, int32_t len) {
-  if (!h) return SABC_ERR_STATE;
-  const int rc = h->eng->set_eps(eps, len);
-  return rc ? hfail(h, rc) : 0;
-}
-int64_t sabc_history_len(const sabc_handle *h) { return h ? h->eng->history_len() : 0; }
-int sabc_get_history(const sabc_handle *h, double *e, double *u, double *r) {
-  if (!h) return SABC_ERR_STATE;
-  h->eng->history(e, u, r);
-  return 0;
-}
-int sabc_clear_history(sabc_handle *h) {
-  if (!h) return SABC_ERR_STATE;
-  h->eng->clear_history();
-  return 0;
-}
-
-int64_t sabc_cdf_len(const sabc_handle *h, int32_t stat) {
-  if (!h || stat < 0 || stat >= h->eng->model().s) return 0;
-  return h->eng->cdf_len()[stat];
-}
-int sabc_get_cdf_knots(sabc_handle *h, int32_t stat, double *out) {
-  if (!h) return SABC_ERR_STATE;
-  return h->be->get_knots(stat, out, sabc_cdf_len(h, stat)) ? hfail(h, SABC_ERR_HIP) : 0;
-}
-int sabc_set_cdf_knots(sabc_handle *h, int32_t stat, const double *knots, int64_t len) {
-  if (!h) return SABC_ERR_STATE;
-  if (h->be->set_knots(stat, knots, len)) return hfail(h, SABC_ERR_BAD_CONFIG);
-  h->eng->set_cdf_len(stat, len);
-  return 0;
-}
 int sabc_cdf_apply(sabc_handle *h, const double *rho, int64_t m, double *u_out) {
-  if (!h) return SABC_ERR_STATE;
+  if (int rc = enter(h)) return rc;
   for (int j = 0; j < h->eng->model().s; ++j)
     if (h->eng->cdf_len()[j] < 3) return hset(h, SABC_ERR_STATE, "ECDF tables are not built yet");
   return h->be->cdf_apply_host(rho, m, u_out) ? hfail(h, SABC_ERR_HIP) : 0;
 }
-int sabc_get_proposal_sigma(const sabc_handle *h, double *sigma) {
-  if (!h) return SABC_ERR_STATE;
-  const int d = h->eng->model().d;
-  for (int i = 0; i < d * d; ++i) sigma[i] = h->eng->sigma()[i];
-  return 0;
-}
-double sabc_last_ess(const sabc_handle *h) { return h ? h->be->last_ess() : 0.0; }
 
 // ---- stand-alone operators -----------------------------------------------------------------
 int sabc_op_build_cdf(int32_t device, const double *x, int64_t n, double *knots_out, int64_t *len_out) {
-  std::string why;
-  int rc = usable_device(device, why);
-  if (rc) { g_err = why; return rc; }
-  if (n < 1) { g_err = "empty input"; return SABC_ERR_EMPTY_CDF; }
-  if (hipSetDevice(device) != hipSuccess) { g_err = "hipSetDevice failed"; return SABC_ERR_HIP; }
+  if (int rc = op_open(device, n < 1 ? "empty input" : nullptr, SABC_ERR_EMPTY_CDF)) return rc;
   DeviceBuffer<double> a, b, k;
   DeviceBuffer<int64_t> meta;
   DeviceBuffer<char> tmp;
@@ -609,11 +304,8 @@ int sabc_op_build_cdf(int32_t device, const double *x, int64_t n, double *knots_
 }
 
 int sabc_op_sort(int32_t device, const double *x, int64_t n, double *out) {
-  std::string why;
-  int rc = usable_device(device, why);
-  if (rc) { g_err = why; return rc; }
+  if (int rc = op_open(device)) return rc;
   if (n <= 0) return 0;
-  if (hipSetDevice(device) != hipSuccess) { g_err = "hipSetDevice failed"; return SABC_ERR_HIP; }
   DeviceBuffer<double> a, b;
   DeviceBuffer<char> tmp;
   size_t bytes = 0;
@@ -629,12 +321,8 @@ int sabc_op_sort(int32_t device, const double *x, int64_t n, double *out) {
 }
 
 int sabc_op_cdf_eval(int32_t device, const double *knots, int64_t len, const double *q, int64_t m, double *out) {
-  std::string why;
-  int rc = usable_device(device, why);
-  if (rc) { g_err = why; return rc; }
-  if (len < 2 || m < 0) { g_err = "bad length"; return SABC_ERR_BAD_CONFIG; }
+  if (int rc = op_open(device, len < 2 || m < 0 ? "bad length" : nullptr)) return rc;
   if (m == 0) return 0;
-  if (hipSetDevice(device) != hipSuccess) { g_err = "hipSetDevice failed"; return SABC_ERR_HIP; }
   DeviceBuffer<double> k, dq, dout;
   hipError_t e = k.alloc((size_t)len);
   if (e == hipSuccess) e = dq.alloc((size_t)m);
@@ -658,13 +346,13 @@ int sabc_op_eps_multi(const double *ubar, int32_t s, double v, double *eps_out) 
 }
 
 int sabc_op_simulate(sabc_handle *h, const double *theta, int64_t m, uint64_t pid0, uint64_t iter, double *rho_out) {
-  if (!h) return SABC_ERR_STATE;
+  if (int rc = enter(h)) return rc;
   return h->be->simulate_host(theta, m, pid0, iter, rho_out) ? hfail(h, SABC_ERR_HIP) : 0;
 }
 
 int sabc_op_simulate_outputs(sabc_handle *h, const double *theta, int64_t m, uint64_t pid0, uint64_t iter, int32_t stream,
                              int32_t n_out, double *rho_out, double *out) {
-  if (!h) return SABC_ERR_STATE;
+  if (int rc = enter(h)) return rc;
   if (stream != SABC_STREAM_UPDATE && stream != SABC_STREAM_PREDICT)
     return hset(h, SABC_ERR_BAD_CONFIG, "sabc_op_simulate_outputs: stream is SABC_STREAM_UPDATE or SABC_STREAM_PREDICT");
   const int rc = h->be->simulate_outputs_host(theta, m, pid0, iter, stream == SABC_STREAM_PREDICT ? kPurposePredict : kPurposeSim, n_out,
@@ -673,16 +361,14 @@ int sabc_op_simulate_outputs(sabc_handle *h, const double *theta, int64_t m, uin
 }
 
 int sabc_op_prior(sabc_handle *h, uint64_t pid0, int64_t m, double *theta_out, double *logpdf_out) {
-  if (!h || !theta_out || !logpdf_out) return SABC_ERR_STATE;
+  if (!theta_out || !logpdf_out) return SABC_ERR_STATE;
+  if (int rc = enter(h)) return rc;
   return h->be->prior_host(pid0, m, theta_out, logpdf_out) ? hfail(h, SABC_ERR_HIP) : 0;
 }
 
 int sabc_op_philox(int32_t device, uint64_t seed, uint64_t pid, uint32_t purpose, uint64_t iter, uint32_t k,
                    uint32_t out_words[4], double out_normals[2]) {
-  std::string why;
-  int rc = usable_device(device, why);
-  if (rc) { g_err = why; return rc; }
-  if (hipSetDevice(device) != hipSuccess) { g_err = "hipSetDevice failed"; return SABC_ERR_HIP; }
+  if (int rc = op_open(device)) return rc;
   DeviceBuffer<uint32_t> w;
   DeviceBuffer<double> z;
   hipError_t e = w.alloc(4);
@@ -696,11 +382,8 @@ int sabc_op_philox(int32_t device, uint64_t seed, uint64_t pid, uint32_t purpose
 
 int sabc_op_normal_pairs(int32_t device, uint64_t seed, uint64_t pid0, uint32_t purpose, uint64_t iter, uint32_t k,
                          int64_t m, double *out_2m) {
-  std::string why;
-  int rc = usable_device(device, why);
-  if (rc) { g_err = why; return rc; }
+  if (int rc = op_open(device)) return rc;
   if (m <= 0) return 0;
-  if (hipSetDevice(device) != hipSuccess) { g_err = "hipSetDevice failed"; return SABC_ERR_HIP; }
   DeviceBuffer<double> d;
   hipError_t e = d.alloc(2 * (size_t)m);
   if (e == hipSuccess) e = (hipError_t)launch_normal_pairs(seed, pid0, purpose, iter, k, m, d.get(), nullptr);
@@ -710,11 +393,7 @@ int sabc_op_normal_pairs(int32_t device, uint64_t seed, uint64_t pid0, uint32_t 
 }
 
 int sabc_op_rng_peak(int32_t device, int64_t n_lanes, int32_t pairs_per_lane, int32_t repeats, double *normals_per_s) {
-  std::string why;
-  int rc = usable_device(device, why);
-  if (rc) { g_err = why; return rc; }
-  if (n_lanes < 1 || pairs_per_lane < 1 || repeats < 1) { g_err = "bad arguments"; return SABC_ERR_BAD_CONFIG; }
-  if (hipSetDevice(device) != hipSuccess) { g_err = "hipSetDevice failed"; return SABC_ERR_HIP; }
+  if (int rc = op_open(device, n_lanes < 1 || pairs_per_lane < 1 || repeats < 1 ? "bad arguments" : nullptr)) return rc;
   DeviceBuffer<double> d;
   hipEvent_t a = nullptr, b = nullptr;
   hipError_t e = d.alloc((size_t)n_lanes);
@@ -734,12 +413,10 @@ int sabc_op_rng_peak(int32_t device, int64_t n_lanes, int32_t pairs_per_lane, in
   return 0;
 }
 
-int64_t sabc_host_syncs(const sabc_handle *h) { return h ? h->eng->host_syncs() : 0; }
 int64_t sabc_kernel_launches(const sabc_handle *h) { return h ? h->be->kernel_launches() : 0; }
-int64_t sabc_collective_calls(const sabc_handle *h) { return h ? h->eng->collective_calls() : 0; }
 
 int sabc_profile_enable(sabc_handle *h, int32_t on) {
-  if (!h) return SABC_ERR_STATE;
+  if (int rc = enter(h)) return rc;
   h->be->profile_enable(on);
   return 0;
 }
@@ -747,7 +424,7 @@ int sabc_profile_enable(sabc_handle *h, int32_t on) {
 int64_t sabc_profile_noops(sabc_handle *h, int32_t kernel) { return h ? h->be->profile_noops(kernel) : 0; }
 
 int sabc_profile_get(sabc_handle *h, int32_t kernel, double *total_ms, int64_t *launches) {
-  if (!h) return SABC_ERR_STATE;
+  if (int rc = enter(h)) return rc;
   return h->be->profile_get(kernel, total_ms, launches) ? hfail(h, SABC_ERR_HIP) : 0;
 }
 

@@ -45,6 +45,8 @@ class Backend {
   // small host <-> backend-memory transfers that complete before they return (counts of the resample exchange)
   virtual int to_backend(double *dst, const double *src_host, int64_t n) = 0;
   virtual int to_host(double *dst_host, const double *src, int64_t n) = 0;
+  // the stream the backend enqueues on, as collective hooks that take backend pointers are handed it (null: none)
+  virtual void *stream_handle() const { return nullptr; }
   // host-simulator mode (SABC_MODEL_HOST): f_dist is a host callback; a backend without it says so
   virtual int set_host_simulator(sabc_simulate_fn, void *) { return -1; }
   virtual int set_host_prior(sabc_prior_sample_fn, sabc_prior_logpdf_fn, void *) { return -1; }   // prior_joint = 2

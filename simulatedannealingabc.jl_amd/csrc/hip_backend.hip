@@ -241,11 +241,6 @@ int HipBackend::to_host(double *dst_host, const double *src, int64_t n) {
   return 0;
 }
 
-double *HipBackend::host_stage(int64_t doubles) {
-  if ((int64_t)stage_.size() < doubles) stage_.resize((size_t)doubles);
-  return stage_.data();
-}
-
 // level 1: bracket only the dominant kernel (k_update) -- every hipEventRecord is a marker packet the
 // queue has to drain, ~4 us of GPU time each, so the other kernels are bracketed only at level 2
 void HipBackend::profile_enable(int level) {

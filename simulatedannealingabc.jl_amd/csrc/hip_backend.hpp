@@ -111,6 +111,7 @@ class HipBackend : public Backend {
   // extras used by the C-ABI layer
   int set_stream(hipStream_t s);
   hipStream_t stream() const { return stream_; }
+  void *stream_handle() const override { return (void *)stream_; }
   int device() const { return device_; }
   const std::string &error() const { return err_; }
   CdfPtrs cdf_ptrs() const;
@@ -122,8 +123,6 @@ class HipBackend : public Backend {
                             double *rho_out, double *out);                           // sabc_op_simulate_outputs
   void profile_enable(int level);
   int profile_get(int kernel, double *total_ms, int64_t *launches);
-  // host staging for collectives that cannot take device pointers
-  double *host_stage(int64_t doubles);
 
  private:
   int check(hipError_t e, const char *what);
@@ -178,7 +177,6 @@ class HipBackend : public Backend {
   DeviceBuffer<char> sort_tmp_;
   size_t sort_tmp_bytes_ = 0;
   DeviceBuffer<int64_t> meta_dev_;
-  std::vector<double> stage_;
   void free_later(void *p);                               // device memory released by end_of_call(), never inside a call
   std::vector<void *> deferred_free_;
   // a buffer that has to grow inside a call: the old allocation goes to the deferred list, never to hipFree

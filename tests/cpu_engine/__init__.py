@@ -1,7 +1,7 @@
 """CPU harness for the product's host engine (TEST INFRASTRUCTURE; see ref_backend.cpp).
 Builds tests/cpu_engine/libsabc_cpu_engine.so with g++ from the product's engine.cpp +
-control.hpp and a Backend made of oracle calls, and exposes it through the same Python handle
-class the product uses."""
+control.hpp, its backend-independent C layer (capi_shared.hpp) and a Backend made of oracle
+calls, and exposes it through the same Python handle class the product uses."""
 import ctypes as C
 import os
 import subprocess
@@ -15,7 +15,7 @@ _SRCS = [
     os.path.join(ROOT, "oracle", "sabc_oracle.c"),
 ]
 _DEPS = _SRCS + [os.path.join(ROOT, "simulatedannealingabc.jl_amd", "csrc", f)
-                 for f in ("engine.hpp", "control.hpp", "host_math.hpp", "sabc_types.hpp", "p2p.hpp", "p2p_setup.hpp")] + \
+                 for f in ("engine.hpp", "control.hpp", "host_math.hpp", "sabc_types.hpp", "p2p.hpp", "p2p_setup.hpp", "capi_shared.hpp")] + \
         [os.path.join(ROOT, "include", "sabc_hip.h"), os.path.join(ROOT, "oracle", "sabc_oracle.h")]
 
 

@@ -5,7 +5,9 @@
 // on a CPU with a Backend whose "kernels" are loops over the oracle's per-particle functions
 // (oracle/sabc_oracle.c).  Purpose: exercise the world > 1 code path with torch.distributed
 // "gloo" where no GPU exists, and give the sharded HIP runs a reference with the SAME shard
-// colouring.  It exports the subset of include/sabc_hip.h the tests need, under the same names.
+// colouring.  What it exports of include/sabc_hip.h is the product's own C layer -- csrc/capi_shared.hpp, the very text
+// libsabc_hip.so is built from: handle, error texts, hook collectives with their host staging, self-test, engine entry
+// points, peer-to-peer set-up -- over the CPU backend below; only sabc_create / sabc_destroy and a few counters are its own.
 #include <atomic>
 #include <chrono>
 #include <cmath>
@@ -20,11 +22,8 @@
 #include "../../simulatedannealingabc.jl_amd/csrc/control.hpp"
 #include "../../simulatedannealingabc.jl_amd/csrc/engine.hpp"
 #include "../../simulatedannealingabc.jl_amd/csrc/p2p.hpp"
-#include "../../simulatedannealingabc.jl_amd/csrc/p2p_setup.hpp"
 
 using namespace sabc;
-
-namespace {
 
 constexpr int kBlockRows = 256;   // same partial-row granularity as the device kernels
 
@@ -67,8 +66,8 @@ class RefBackend : public Backend {
     for (int r = 0; r < rows; ++r) std::memcpy(dst + (size_t)r * dp, src + (size_t)r * sp, (size_t)count * sizeof(double));
     return 0;
   }
-  int to_backend(double *dst, const double *src, int64_t n) override { std::memcpy(dst, src, (size_t)n * sizeof(double)); return 0; }
-  int to_host(double *dst, const double *src, int64_t n) override { std::memcpy(dst, src, (size_t)n * sizeof(double)); return 0; }
+  int to_backend(double *dst, const double *src, int64_t n) override { if (n > 0) std::memcpy(dst, src, (size_t)n * sizeof(double)); return 0; }
+  int to_host(double *dst, const double *src, int64_t n) override { if (n > 0) std::memcpy(dst, src, (size_t)n * sizeof(double)); return 0; }
 
   int prior_simulate() override {
     const int d = m_.d, s = m_.s; const int64_t cap = sh_.cap;
@@ -672,44 +671,16 @@ class RefBackend : public Backend {
   double ess_ = 0.0;
 };
 
-class NoColl : public Collectives {
- public:
-  int allreduce_sum(double *, int64_t) override { return 0; }
-  int allgather(const double *, double *, int64_t) override { return -1; }
-  bool usable() const override { return false; }
-};
+// the product's own C layer (csrc/capi_shared.hpp) over this backend; there is no device to make current
+using CapiBackend = RefBackend;
+static bool capi_make_current(CapiBackend *) { return true; }
+#include "../../simulatedannealingabc.jl_amd/csrc/capi_shared.hpp"
 
-class HookColl : public Collectives {
- public:
-  HookColl(sabc_allreduce_fn ar, sabc_allgather_fn ag, void *ctx, int world) : ar_(ar), ag_(ag), ctx_(ctx), world_(world) {}
-  void set_alltoallv(sabc_alltoallv_fn fn) { a2a_ = fn; }
-  bool has_alltoallv() const override { return a2a_ != nullptr; }
-  int alltoallv(const double *send, const int64_t *sc, double *recv, const int64_t *rc) override {
-    return a2a_(ctx_, send, sc, recv, rc, world_, nullptr);
-  }
-  int allreduce_sum(double *buf, int64_t count) override { return ar_(ctx_, buf, count, nullptr); }
-  int allgather(const double *send, double *recv, int64_t count) override { return ag_(ctx_, send, recv, count, nullptr); }
- private:
-  sabc_allreduce_fn ar_; sabc_allgather_fn ag_; void *ctx_; int world_;
-  sabc_alltoallv_fn a2a_ = nullptr;
-};
-
-thread_local std::string g_err;
-
-}  // namespace
-
-struct sabc_handle {
-  Engine *eng = nullptr;
-  RefBackend *be = nullptr;
-  Collectives *coll = nullptr;
-  std::string err;
-};
-
+// what depends on the backend: the handle's life, and the hooks only this harness has
 extern "C" {
 
-int sabc_abi_version(void) { return SABC_ABI_VERSION; }
-const char *sabc_last_global_error(void) { return g_err.c_str(); }
 int sabc_device_count(void) { return 0; }
+int64_t sabc_kernel_launches(const sabc_handle *) { return 0; }
 
 static std::atomic<int64_t> g_parked{0};
 void sabc_destroy(sabc_handle *h) {
@@ -725,7 +696,7 @@ int sabc_create(const sabc_config *cfg, sabc_handle **out) {
   *out = nullptr;
   sabc_handle *h = new sabc_handle();
   h->be = new RefBackend();
-  h->coll = new NoColl();
+  h->coll = new NoCollectives();
   h->eng = new Engine(*cfg, h->be, h->coll);
   const int rc = h->eng->validate();
   if (rc) { g_err = h->eng->error(); sabc_destroy(h); return rc; }
@@ -734,126 +705,10 @@ int sabc_create(const sabc_config *cfg, sabc_handle **out) {
   return 0;
 }
 
-const char *sabc_last_error(const sabc_handle *h) { return h ? h->err.c_str() : g_err.c_str(); }
-
-int sabc_set_collectives(sabc_handle *h, sabc_allreduce_fn ar, sabc_allgather_fn ag, void *ctx, int) {
-  delete h->coll;
-  h->coll = new HookColl(ar, ag, ctx, h->eng->shard().world);
-  h->eng->set_collectives(h->coll);
-  return 0;
-}
-
-int sabc_set_alltoallv(sabc_handle *h, sabc_alltoallv_fn fn) {
-  HookColl *c = dynamic_cast<HookColl *>(h->coll);
-  if (!c || !fn) { h->err = "sabc_set_alltoallv needs sabc_set_collectives first"; return SABC_ERR_COMM; }
-  c->set_alltoallv(fn);
-  return 0;
-}
-
-int64_t sabc_comm_bytes(const sabc_handle *h) { return h->eng->comm_bytes(); }
-
-int sabc_comm_selftest(sabc_handle *h) {
-  const Shard &sh = h->eng->shard();
-  const int world = sh.world;
-  if (world == 1) return 0;
-  double *g = h->be->gather_buffer((int64_t)(world + 1) * 4);
-  g[0] = sh.rank + 1; g[1] = 2.0; g[2] = 3.0; g[3] = 100 + sh.rank;
-  if (h->coll->allgather(g, g + 4, 4) || h->coll->allreduce_sum(g, 4)) { h->err = "self-test collective failed"; return SABC_ERR_COMM; }
-  bool ok = g[0] == 0.5 * world * (world + 1) && g[1] == 2.0 * world;
-  for (int r = 0; r < world; ++r) ok = ok && g[4 + 4 * r] == (double)(r + 1) && g[4 + 4 * r + 3] == (double)(100 + r);
-  if (!ok) { h->err = "self-test collective gave wrong values"; return SABC_ERR_COMM; }
-  if (h->coll->has_alltoallv()) {
-    std::vector<int64_t> sc((size_t)world), rc((size_t)world);
-    int64_t ns = 0, nr = 0;
-    for (int p = 0; p < world; ++p) { sc[(size_t)p] = rc[(size_t)p] = sh.rank + p + 1; ns += sc[(size_t)p]; nr += rc[(size_t)p]; }
-    std::vector<double> out((size_t)ns), in((size_t)nr, 0.0);
-    int64_t o = 0;
-    for (int p = 0; p < world; ++p)
-      for (int64_t k = 0; k < sc[(size_t)p]; ++k) out[(size_t)o++] = 1000.0 * sh.rank + p;
-    if (h->coll->alltoallv(out.data(), sc.data(), in.data(), rc.data())) { h->err = "self-test alltoallv failed"; return SABC_ERR_COMM; }
-    o = 0;
-    for (int p = 0; p < world; ++p)
-      for (int64_t k = 0; k < rc[(size_t)p]; ++k)
-        if (in[(size_t)o++] != 1000.0 * p + sh.rank) { h->err = "self-test alltoallv gave wrong words"; return SABC_ERR_COMM; }
-  }
-  return 0;
-}
-
-int sabc_initialize(sabc_handle *h, int64_t n_simulation) {
-  const int rc = h->eng->initialize(n_simulation);
-  if (rc) h->err = h->eng->error();
-  return rc;
-}
-int sabc_update(sabc_handle *h, const sabc_update_args *a) {
-  const int rc = h->eng->update(*a);
-  if (rc) h->err = h->eng->error();
-  return rc;
-}
-int64_t sabc_n_global(const sabc_handle *h) { return h ? h->eng->shard().n_global : 0; }
-int64_t sabc_n_local(const sabc_handle *h) { return h->eng->shard().n_local; }
-int64_t sabc_local_offset(const sabc_handle *h) { return h->eng->shard().gid0; }
-int sabc_get_population(sabc_handle *h, double *t, double *u, double *r) { return h->be->download(t, u, r); }
-int sabc_set_population(sabc_handle *h, const double *t, const double *u, const double *r) {
-  h->be->upload(t, u, r); h->eng->mark_initialized(); return 0;
-}
-int sabc_get_counters(const sabc_handle *h, int64_t out[4]) { h->eng->counters(out); return 0; }
-int sabc_set_counters(sabc_handle *h, const int64_t in[4]) { h->eng->set_counters(in); return 0; }
-int sabc_get_epsilon(const sabc_handle *h, double *eps, int32_t *len) {
-  for (int i = 0; i < h->eng->eps_len(); ++i) eps[i] = h->eng->eps()[i];
-  if (len) *len = h->eng->eps_len();
-  return 0;
-}
-int sabc_set_epsilon(sabc_handle *h, const double *eps, int32_t len) { return h->eng->set_eps(eps, len); }
-int64_t sabc_history_len(const sabc_handle *h) { return h->eng->history_len(); }
-int sabc_get_history(const sabc_handle *h, double *e, double *u, double *r) { h->eng->history(e, u, r); return 0; }
-int sabc_clear_history(sabc_handle *h) { h->eng->clear_history(); return 0; }
-int64_t sabc_cdf_len(const sabc_handle *h, int32_t stat) { return h->eng->cdf_len()[stat]; }
-int sabc_get_cdf_knots(sabc_handle *h, int32_t stat, double *out) { return h->be->get_knots(stat, out, h->eng->cdf_len()[stat]); }
-int sabc_get_proposal_sigma(const sabc_handle *h, double *sigma) {
-  const int d = h->eng->model().d;
-  for (int i = 0; i < d * d; ++i) sigma[i] = h->eng->sigma()[i];
-  return 0;
-}
-double sabc_last_ess(const sabc_handle *h) { return h->be->last_ess(); }
-int64_t sabc_host_syncs(const sabc_handle *h) { return h->eng->host_syncs(); }
-int64_t sabc_collective_calls(const sabc_handle *h) { return h->eng->collective_calls(); }
-int64_t sabc_kernel_launches(const sabc_handle *) { return 0; }
-int64_t sabc_persistent_launches(const sabc_handle *h) { return h->eng->persistent_launches(); }
-int32_t sabc_persistent_lanes(const sabc_handle *h) { return h->eng->persistent_lanes(); }
-int64_t sabc_persistent_fallbacks(const sabc_handle *h) { return h->eng->persistent_fallbacks(); }
-
-// the peer-to-peer entry points, over the in-process emulation above (shards = host threads of this process)
-int sabc_comm_p2p_descriptor(sabc_handle *h, void *out) {
-  if (h->be->p2p_descriptor((P2PDesc *)out)) { h->err = h->be->error(); return SABC_ERR_COMM; }
-  return 0;
-}
-int sabc_comm_p2p_init(sabc_handle *h, const void *all) {
-  if (!all || h->be->p2p_init((const P2PDesc *)all)) { h->err = "peer-to-peer descriptors do not match"; return SABC_ERR_COMM; }
-  return 0;
-}
-int sabc_comm_p2p_selftest(sabc_handle *h) {
-  if (h->be->p2p_selftest()) { h->err = h->be->error(); return SABC_ERR_COMM; }
-  return 0;
-}
-// the product's own set-up sequence (csrc/p2p_setup.hpp) over this backend
-int sabc_comm_p2p_setup(sabc_handle *h) {
-  std::string note;
-  const int rc = p2p_setup_sequence(h->be, h->coll, h->eng->shard(), h->eng->host_mode(), &note);
-  h->err = note;
-  return rc == 1 ? (h->eng->p2p() ? 1 : 0) : rc;
-}
-int sabc_comm_p2p_set_destroy_wait(sabc_handle *h, double ms) { h->be->p2p_set_destroy_wait(ms); return 0; }
 int64_t sabc_comm_p2p_parked_bytes(void) { return g_parked.load(); }          // (here: parked backends)
-int sabc_comm_p2p_inject_stale(sabc_handle *h, int32_t n) { h->be->p2p_inject_stale(n); return 0; }
-int sabc_comm_p2p_inject_loss(sabc_handle *h, int32_t n) { h->be->p2p_inject_loss(n); return 0; }
 // harness only: 1 = this shard's next descriptors cannot be exported, 2 = it cannot map its peers, 0 = back to normal
 int sabc_test_p2p_inject_setup_failure(sabc_handle *h, int32_t what) { h->be->p2p_inject_setup_failure(what); return 0; }
 // harness only: which of its two population buffers the shard stands on
 int sabc_test_cur_parity(const sabc_handle *h) { return h->be->cur_parity(); }
-int sabc_comm_p2p_set_timeout(sabc_handle *h, double ms) { h->be->p2p_set_timeout(ms); return 0; }
-int sabc_comm_p2p_disable(sabc_handle *h) { h->be->p2p_disable(); return 0; }
-int sabc_comm_p2p_active(const sabc_handle *h) { return h->eng->p2p() ? 1 : 0; }
-int64_t sabc_comm_p2p_fallbacks(const sabc_handle *h) { return h->eng->p2p_fallbacks(); }
-int sabc_comm_p2p_inject_silence(sabc_handle *h, int32_t n) { h->be->p2p_inject_silence(n); return 0; }
 
 }  // extern "C"
