@@ -214,6 +214,18 @@ SABC_API int64_t     sabc_host_callback_calls(const sabc_handle *h);
                                        trial (at most 64); lambda <= 2^30
        rng.binomial(n, p)              n <= 0 or p <= 0: 0, p >= 1: n, no block | n min(p, 1 - p) < 10: inversion, one block |
                                        else Hoermann's BTRS, a block per trial (at most 64)
+   BINARY32 DRAWS, for simulators whose noise needs no more (an SDE path, observation noise): four normals from the 128 bits
+   that give two in f64, half the generator's instructions per normal.  Each call consumes WHOLE blocks of the same stream and
+   the same block counter, so they mix freely with every draw above; all work with a lane, a quad or a row of lanes per particle.
+       rng.quad_f32(z0, z1, z2, z3)    one block: four N(0,1) floats, (z0, z1) from its words (x, y), (z2, z3) from (z, w);
+                                       |z| <= sqrt(66 ln 2) = 6.7637 (the radius uniform is at least 2^-33)
+       rng.uniform_quad_f32(u0, u1, u2, u3)
+                                       one block: u_i = ((w_i >> 9) + 1/2) 2^-23, exact in binary32, in (0, 1)
+       rng.for_quads_f32(n, [&](float z0, float z1, float z2, float z3) { ... })
+                                       the normals of the next n blocks, in stream order: the loop to draw the bulk with
+   Every step of them is an exact bit operation, a table read, an fma / product / sum of binary32 or a correctly rounded square
+   root: a CPU restates them bit for bit (tests/elementary_f32_ref.py).  theta, params, rho_out, sabc::data_at and sabc::emit
+   stay double.
    With sabc_config::prior_joint = 3 the same source also defines the PRIOR -- any distribution, evaluated inside the fused
    kernel (SimulatedAnnealingABC.jl:151 takes any Distributions.Distribution):
        __device__ void   sabc_user_prior_sample(const double *params, sabc::NormalStream &rng, double *theta_out);
@@ -410,6 +422,15 @@ SABC_API int sabc_op_normal_pairs(int32_t device, uint64_t seed, uint64_t pid0, 
    on n_lanes lanes: the VALU ceiling of every simulator that draws from it */
 SABC_API int sabc_op_rng_peak(int32_t device, int64_t n_lanes, int32_t pairs_per_lane, int32_t repeats,
                               double *normals_per_s);
+
+/* The binary32 twins (csrc/device_rng.hpp, namespace f32: four normals per Philox block).  The four normals of block k
+   for particles pid0..pid0+m-1 (out: z0,z1,z2,z3 interleaved), bit for bit what tests/elementary_f32_ref.py restates ... */
+SABC_API int sabc_op_normal_quads_f32(int32_t device, uint64_t seed, uint64_t pid0, uint32_t purpose, uint64_t iter,
+                                      uint32_t k, int64_t m, float *out_4m);
+/* ... and the rate (normals/s) of the bare loop of NormalStream::for_quads_f32.  A library without a device
+   answers SABC_ERR_NO_DEVICE to both. */
+SABC_API int sabc_op_rng_peak_f32(int32_t device, int64_t n_lanes, int32_t quads_per_lane, int32_t repeats,
+                                  double *normals_per_s);
 
 /* ---- measurement ---- */
 enum { SABC_KERNEL_UPDATE = 0, SABC_KERNEL_REDUCE = 1, SABC_KERNEL_RESAMPLE = 2, SABC_KERNEL_INIT = 3,

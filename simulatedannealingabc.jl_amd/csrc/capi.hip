@@ -21,6 +21,7 @@
 
 using CapiBackend = sabc::HipBackend;
 static bool capi_make_current(CapiBackend *be) { return hipSetDevice(be->device()) == hipSuccess; }
+#define SABC_CAPI_DEVICE_OPS 1
 #include "capi_shared.hpp"
 
 namespace {
@@ -130,6 +131,40 @@ int op_open(int32_t device, const char *bad_args = nullptr, int bad_rc = SABC_ER
   if (int rc = usable_device(device)) return rc;
   if (bad_args) { g_err = bad_args; return bad_rc; }
   if (hipSetDevice(device) != hipSuccess) { g_err = "hipSetDevice failed"; return SABC_ERR_HIP; }
+  return 0;
+}
+
+// the device halves of capi_shared.hpp's stand-alone operators
+int device_op_normal_quads_f32(int32_t device, uint64_t seed, uint64_t pid0, uint32_t purpose, uint64_t iter, uint32_t k, int64_t m,
+                               float *out_4m) {
+  if (int rc = op_open(device)) return rc;
+  if (m <= 0) return 0;
+  DeviceBuffer<float> d;
+  hipError_t e = d.alloc(4 * (size_t)m);
+  if (e == hipSuccess) e = (hipError_t)launch_normal_quads_f32(seed, pid0, purpose, iter, k, m, d.get(), nullptr);
+  if (e == hipSuccess) e = hipMemcpy(out_4m, d.get(), (size_t)m * 16, hipMemcpyDeviceToHost);
+  if (e != hipSuccess) { g_err = hipGetErrorString(e); return SABC_ERR_HIP; }
+  return 0;
+}
+
+int device_op_rng_peak_f32(int32_t device, int64_t n_lanes, int32_t quads_per_lane, int32_t repeats, double *normals_per_s) {
+  if (int rc = op_open(device)) return rc;
+  DeviceBuffer<float> d;
+  hipEvent_t a = nullptr, b = nullptr;
+  hipError_t e = d.alloc((size_t)n_lanes);
+  if (e == hipSuccess) e = hipEventCreate(&a);
+  if (e == hipSuccess) e = hipEventCreate(&b);
+  if (e == hipSuccess) e = (hipError_t)launch_rng_peak_f32(1, quads_per_lane, n_lanes, d.get(), nullptr);   // warm-up
+  if (e == hipSuccess) e = hipEventRecord(a, nullptr);
+  for (int r = 0; r < repeats && e == hipSuccess; ++r) e = (hipError_t)launch_rng_peak_f32(2 + r, quads_per_lane, n_lanes, d.get(), nullptr);
+  if (e == hipSuccess) e = hipEventRecord(b, nullptr);
+  if (e == hipSuccess) e = hipEventSynchronize(b);
+  float ms = 0.f;
+  if (e == hipSuccess) e = hipEventElapsedTime(&ms, a, b);
+  if (a) (void)hipEventDestroy(a);
+  if (b) (void)hipEventDestroy(b);
+  if (e != hipSuccess) { g_err = hipGetErrorString(e); return SABC_ERR_HIP; }
+  *normals_per_s = 4.0 * (double)quads_per_lane * (double)n_lanes * (double)repeats / ((double)ms * 1e-3);
   return 0;
 }
 

@@ -8,6 +8,8 @@
 //                                              p2p_inject_* knobs)
 //   bool capi_make_current(CapiBackend *);    (the body of the prologue: make the handle's device the thread's current one)
 // and, after it, the entry points that do depend on the backend (sabc_create and sabc_destroy among them).
+// An includer with a device also defines SABC_CAPI_DEVICE_OPS before the #include and, after it, the device halves of the
+// stand-alone operators declared below (device_op_*); without it those operators answer SABC_ERR_NO_DEVICE.
 #pragma once
 #include <cstring>
 #include <string>
@@ -104,6 +106,18 @@ class CallbackCollectives : public Collectives {
   bool dev_;
   std::vector<double> stage_;
 };
+
+#if defined(SABC_CAPI_DEVICE_OPS)
+// the device halves: a usable device made current, the launch, the copy back; the error text in g_err
+int device_op_normal_quads_f32(int32_t device, uint64_t seed, uint64_t pid0, uint32_t purpose, uint64_t iter, uint32_t k, int64_t m,
+                               float *out_4m);
+int device_op_rng_peak_f32(int32_t device, int64_t n_lanes, int32_t quads_per_lane, int32_t repeats, double *normals_per_s);
+#endif
+
+int no_device_op(const char *name) {
+  g_err = std::string(name) + ": this library has no device";
+  return SABC_ERR_NO_DEVICE;
+}
 
 }  // namespace
 
@@ -339,6 +353,28 @@ int sabc_get_proposal_sigma(const sabc_handle *h, double *sigma) {
   return 0;
 }
 double sabc_last_ess(const sabc_handle *h) { return enter(const_cast<sabc_handle *>(h)) ? 0.0 : h->be->last_ess(); }
+
+// ---- stand-alone operators on the binary32 draws (csrc/device_rng.hpp, namespace f32) ----
+int sabc_op_normal_quads_f32(int32_t device, uint64_t seed, uint64_t pid0, uint32_t purpose, uint64_t iter, uint32_t k, int64_t m,
+                             float *out_4m) {
+  if (m > 0 && !out_4m) { g_err = "sabc_op_normal_quads_f32: null output"; return SABC_ERR_BAD_CONFIG; }
+#if defined(SABC_CAPI_DEVICE_OPS)
+  return device_op_normal_quads_f32(device, seed, pid0, purpose, iter, k, m, out_4m);
+#else
+  (void)device; (void)seed; (void)pid0; (void)purpose; (void)iter; (void)k;
+  return no_device_op("sabc_op_normal_quads_f32");
+#endif
+}
+
+int sabc_op_rng_peak_f32(int32_t device, int64_t n_lanes, int32_t quads_per_lane, int32_t repeats, double *normals_per_s) {
+  if (!normals_per_s || n_lanes < 1 || quads_per_lane < 1 || repeats < 1) { g_err = "sabc_op_rng_peak_f32: bad arguments"; return SABC_ERR_BAD_CONFIG; }
+#if defined(SABC_CAPI_DEVICE_OPS)
+  return device_op_rng_peak_f32(device, n_lanes, quads_per_lane, repeats, normals_per_s);
+#else
+  (void)device;
+  return no_device_op("sabc_op_rng_peak_f32");
+#endif
+}
 
 int64_t sabc_host_syncs(const sabc_handle *h) { return h ? h->eng->host_syncs() : 0; }
 int64_t sabc_collective_calls(const sabc_handle *h) { return h ? h->eng->collective_calls() : 0; }

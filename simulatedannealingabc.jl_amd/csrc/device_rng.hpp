@@ -415,6 +415,182 @@ __device__ __forceinline__ double team_pick(const double v, const uint32_t j) {
   }
 }
 
+// ---- f32 draws: four N(0,1) per Philox block (NormalStream::quad_f32 / for_quads_f32) -------------------------------------
+// A block w = (x, y, z, w) gives (z0, z1) from (x, y) and (z2, z3) from (z, w).  Of a pair (a, b):
+//   radius uniform  u = fma((float)a, 2^-32, 2^-33): the u32 -> f32 conversion rounds to nearest even (exact below 2^24), so
+//                   u in [2^-33, 1] with full resolution where the tail is; u == 1 gives the radius 0, never a NaN
+//   angle, in turns (b >> 8) 2^-24, exact; its 32nd parts are split in integers: k = rint(32 turns) picks the row of sct and
+//                   32 turns - k = (fi - 2^26) 2^-27 with fi = (b + 2^26) & 0x07FFFF00 is exact in binary32
+//   z0 = fma(R, cos, +0), z1 = fma(R, sin, +0) with R = sqrt(-2 log u): |z| <= sqrt(66 ln 2) = 6.7637 (u = 2^-33).  (The fma
+//                   against +0: a plain product could be contracted with the caller's next addition, and the draw a simulator
+//                   sees would no longer be a rounded value a CPU can restate; a -0 becomes +0.)
+// Every step is an exact bit operation, a read of the f64 tables in LDS (RngTables, unchanged) rounded to binary32, an fma / mul /
+// add in binary32, or the correctly rounded square root: tests/elementary_f32_ref.py restates it in NumPy and the device gives
+// those bits (tests/test_gpu_f32_draws.py).  No v_log_f32 / v_sin_f32 / v_cos_f32 / v_rcp_f32 / v_rsq_f32.
+// The two pairs of a block run side by side in the halves of packed instructions (v_pk_fma_f32 / v_pk_mul_f32 / v_pk_add_f32):
+// left to itself the compiler packs next to nothing here, so the values are spelled as two-element vectors.
+// Worst error of a normal against exact arithmetic applied to the same u and angle, measured by tests/test_f32_draws.py over
+// its edge words and 2e5 random ones: 3.53 ulp of binary32 (asserted: 4).
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+
+namespace f32 {
+
+__device__ __forceinline__ f32x2 fma2(const f32x2 a, const f32x2 b, const f32x2 c) { return __builtin_elementwise_fma(a, b, c); }
+__device__ __forceinline__ f32x2 splat(const float v) { return f32x2{v, v}; }
+__device__ __forceinline__ f32x2 as_f32(const u32x2 v) { return f32x2{__uint_as_float(v.x), __uint_as_float(v.y)}; }
+__device__ __forceinline__ u32x2 as_u32(const f32x2 v) { return u32x2{__float_as_uint(v.x), __float_as_uint(v.y)}; }
+
+// the correctly rounded sqrt(x) for x = 0 or a normal x (here: x in [6e-8, 46]): v_sqrt_f32 is within one ulp, so the root is the
+// seed or one of its neighbours, and the signs of two exact residuals say which -- x - y_down y <= 0: the neighbour below,
+// x - y_up y > 0: the one above.  (What the compiler emits for sqrtf(), minus the scaling of tiny inputs.  x = 0: the seed is 0,
+// its lower neighbour a NaN whose comparison fails, the upper one's residual is 0: the result is 0.)
+__device__ __forceinline__ f32x2 sqrt_cr(const f32x2 x) {
+  const f32x2 y = f32x2{__builtin_amdgcn_sqrtf(x.x), __builtin_amdgcn_sqrtf(x.y)};
+  const f32x2 yd = as_f32(as_u32(y) - 1u), yu = as_f32(as_u32(y) + 1u);
+  const f32x2 rd = fma2(-yd, y, x), ru = fma2(-yu, y, x);
+  f32x2 r;
+  r.x = rd.x <= 0.0f ? yd.x : y.x;
+  r.y = rd.y <= 0.0f ? yd.y : y.y;
+  r.x = ru.x > 0.0f ? yu.x : r.x;
+  r.y = ru.y > 0.0f ? yu.y : r.y;
+  return r;
+}
+
+// The rows of RngTables rounded to binary32, one array per column so that the entries of a block's two pairs load into the two
+// halves of a packed operand: 1672 bytes of LDS in the kernels that call for_quads_f32, none in the others (RngTables and the
+// kernels' prologue stay as they are).  Filled by for_quads_f32 itself, which runs where a workgroup barrier cannot stand
+// (behind a kernel's divergent return, inside a simulator): the lanes of the wave that are active at the call write ALL rows,
+// the r-th active lane rows r, r + count, ..., and a wave reads only after its own writes -- LDS keeps a wave's accesses in
+// order.  Other waves of the workgroup write the same rows with the same values at their own time, which changes nothing a
+// reader can see.  The conversions (two per lookup with the f64 rows, 16 VALU instructions per trip of the loop) are paid
+// once per call.
+// The two columns of a table lie 257 words apart: out of reach of the two-address LDS reads (ds_read2_b32: 255 words,
+// ds_read2st64_b32: multiples of 64), into which the compiler would merge the reads of lx[i] and ly[i] -- the words of ONE pair
+// would land in a register pair, and moves would have to re-pair them for the packed instructions.
+struct TablesF32 {
+  float lx[128];                 // logt[i].x
+  float sn[33];                  // sct[k].x
+  float pad[96];
+  float ly[128];                 // logt[i].y, at word 257
+  float cs[33];                  // sct[k].y, at word 385 = 128 + 257
+};
+__device__ __forceinline__ TablesF32 &tables_f32() {
+  __shared__ TablesF32 t;
+  return t;
+}
+__device__ __forceinline__ void tables_f32_fill() {
+  const RngTables &T = rng_tables();
+  TablesF32 &t = tables_f32();
+  const uint64_t active = __builtin_amdgcn_ballot_w64(true);
+  const int count = __popcll(active);
+  const int rank = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(active >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)active, 0u));
+  for (int i = rank; i < 128; i += count) {
+    const double2 e = T.logt[i];
+    t.lx[i] = (float)e.x;
+    t.ly[i] = (float)e.y;
+  }
+  for (int i = rank; i < 33; i += count) {
+    const double2 e = T.sct[i];
+    t.sn[i] = (float)e.x;
+    t.cs[i] = (float)e.y;
+  }
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// -2 log(u) for the two radius uniforms of a block, u in [2^-33, 1].  The scheme of neg2_log_tab on the same table, in binary32:
+// the 7 leading mantissa bits, rounded, pick the bin; c = u with the mantissa rounded to those bits (a mask), d = u - c is exact,
+// s = d (-2 / c) with the table's -2 inv_i rounded to binary32 and scaled by the power of two in its exponent field, and
+// -2 log1p(r) = s + s^2 (1/4 + s/12 + s^2/32) (the next term is below 2^-26 of the result).  (Not fma(u, -2 inv, 2): the rounded
+// inv_i no longer matches the table's logarithm, 2^-24 absolutely, which is 2^-15 of a result near u = 1.)
+// (TAB32: the rows from TablesF32, filled by the caller, and not converted from RngTables -- the same values.)
+template <bool TAB32>
+__device__ __forceinline__ f32x2 neg2_log(const f32x2 u) {
+  const u32x2 t = as_u32(u) + 0x8000u;                  // half a bin: 1 << 15 of the 23 mantissa bits
+  const u32x2 tp = t + (75u << 16);                     // carry when the rounded mantissa is >= 53/128
+  const u32x2 nE = 127u - (tp >> 23);                   // -E, 0..33
+  const u32x2 i = (t >> 16) & 127u;
+  f32x2 ex, ey;
+  if constexpr (TAB32) {
+    const TablesF32 &T = tables_f32();
+    ex = f32x2{T.lx[i.x], T.lx[i.y]};
+    ey = f32x2{T.ly[i.x], T.ly[i.y]};
+  } else {
+    const double2 e0 = rng_tables().logt[i.x], e1 = rng_tables().logt[i.y];
+    ex = f32x2{(float)e0.x, (float)e1.x};
+    ey = f32x2{(float)e0.y, (float)e1.y};
+  }
+  const f32x2 c = as_f32(t & 0xFFFF0000u);
+  ex = as_f32(as_u32(ex) + (nE << 23));
+  const f32x2 s = (u - c) * ex;
+  f32x2 p = fma2(s, splat(1.0f / 32.0f), splat(1.0f / 12.0f));
+  p = fma2(p, s, splat(0.25f));
+  const f32x2 l = fma2(s * s, p, s);
+  const f32x2 nEf = f32x2{(float)(int)nE.x, (float)(int)nE.y};
+  return fma2(nEf, splat(0x1.62e43p+0f), ey) + l;      // 2 ln 2
+}
+
+// the normals of one block
+template <bool TAB32 = false>
+__device__ __forceinline__ void box_muller_quad(const u32x4 w, float &z0, float &z1, float &z2, float &z3) {
+  const f32x2 u = fma2(f32x2{(float)w.x, (float)w.z}, splat(0x1p-32f), splat(0x1p-33f));
+  const f32x2 R = sqrt_cr(neg2_log<TAB32>(u));
+  const u32x2 t2 = u32x2{w.y, w.w} + 0x04000000u;       // + half a 32nd of a turn; wraps to row 0 where row 32 would be
+  const u32x2 fi = t2 & 0x07FFFF00u;
+  const u32x2 k = t2 >> 27;
+  f32x2 S, C;
+  if constexpr (TAB32) {
+    const TablesF32 &T = tables_f32();
+    S = f32x2{T.sn[k.x], T.sn[k.y]};
+    C = f32x2{T.cs[k.x], T.cs[k.y]};
+  } else {
+    const double2 sc0 = rng_tables().sct[k.x], sc1 = rng_tables().sct[k.y];
+    S = f32x2{(float)sc0.x, (float)sc1.x};
+    C = f32x2{(float)sc0.y, (float)sc1.y};
+  }
+  // r = (pi / 16) (32 turns - k): one rounding, of the product of the exact difference with the constant
+  const f32x2 r = fma2(f32x2{(float)fi.x, (float)fi.y}, splat(0x1.921fb6p-30f), splat(-0x1.921fb6p-4f));
+  const f32x2 r2 = r * r;
+  const f32x2 sr = fma2(r * r2, fma2(r2, splat(1.0f / 120.0f), splat(-1.0f / 6.0f)), r);     // sin r, |r| <= pi / 32
+  const f32x2 q = fma2(r2, splat(1.0f / 24.0f), splat(-0.5f)) * r2;                          // cos r - 1
+  const f32x2 sn = fma2(C, sr, fma2(S, q, S));
+  const f32x2 cs = fma2(-S, sr, fma2(C, q, C));
+  const f32x2 a = fma2(R, cs, splat(0.0f)), b = fma2(R, sn, splat(0.0f));
+  z0 = a.x; z1 = b.x; z2 = a.y; z3 = b.y;
+}
+
+// four U(0,1) draws of one block: ((w_i >> 9) + 1/2) 2^-23, exact in binary32 and in (0, 1).  (Not 24 bits: (n + 1/2) 2^-24 is
+// no binary32 number from n = 2^23 on, and rounded to nearest even the last word, n = 2^24 - 1, gives 1.)
+__device__ __forceinline__ void uniform_quad(const u32x4 w, float &u0, float &u1, float &u2, float &u3) {
+  const f32x2 a = fma2(f32x2{(float)(w.x >> 9), (float)(w.y >> 9)}, splat(0x1p-23f), splat(0x1p-24f));
+  const f32x2 b = fma2(f32x2{(float)(w.z >> 9), (float)(w.w >> 9)}, splat(0x1p-23f), splat(0x1p-24f));
+  u0 = a.x; u1 = a.y; u2 = b.x; u3 = b.y;
+}
+
+}  // namespace f32
+
+// team_pick_ct / team_pick for a binary32 value: one DPP move
+template <int W, int J>
+__device__ __forceinline__ float team_pick_ct_f32(const float v) {
+  static_assert((W == 4 || W == 16) && J >= 0 && J < W, "a quad or a row of 16 lanes");
+  constexpr int ctrl = W == 4 ? J * 0x55 : 0x150 + J;
+  int r = __builtin_amdgcn_update_dpp(0, __float_as_int(v), ctrl, 0xF, 0xF, true);
+  // the move stays a move: folded into a consumer that is a 64-bit instruction (a simulator's (double)z is v_cvt_f64_f32), the
+  // quad_perm control is one such instructions do not have, and the compiler's own check then rejects what its combiner made
+  asm("" : "+v"(r));
+  return __int_as_float(r);
+}
+template <int W, int J0 = 0, int N = W>
+__device__ __forceinline__ float team_pick_f32(const float v, const uint32_t j) {
+  if constexpr (N == 1) {
+    return team_pick_ct_f32<W, J0>(v);
+  } else {
+    return (j & (uint32_t)(N / 2)) ? team_pick_f32<W, J0 + N / 2, N / 2>(v, j) : team_pick_f32<W, J0, N / 2>(v, j);
+  }
+}
+
 // simulated pairs per loop trip of NormalStream::for_pairs with a lane per particle: independent Philox / Box-Muller chains for
 // the scheduler (k_update<1,1,1,0>: 92 -> 62 VGPRs, 246 -> ~240 us at n = 1e6); the draws are still handed out in stream order
 constexpr int kSimUnroll = 2;
@@ -454,6 +630,9 @@ struct NormalStream {
   int buf_block;                 // coop: first block of the group of W this lane holds one block of (-1: none) ...
   bool buf_uniform;              // ... as uniforms (uniform_pair) or as a Box-Muller pair
   double b0, b1;
+  int fbuf_block;                // the same for the binary32 draws (quad_f32 / uniform_quad_f32), a buffer of their own
+  bool fbuf_uniform;
+  float fb0, fb1, fb2, fb3;
   // where sabc::emit puts the outputs of THIS simulation: output i at out[i * out_stride], i < out_n.  Null from every
   // constructor: only the forward run (Sim<SABC_MODEL_USER>::run_out) sets a destination, so in every other kernel
   // the null is a constant after inlining and what a simulator does for its outputs is dead code there
@@ -461,7 +640,8 @@ struct NormalStream {
   long long out_stride, out_n;
   __device__ __forceinline__ NormalStream(uint64_t seed_, uint64_t pid_, uint32_t purpose_, uint64_t iter_, int coop_ = 0)
       : seed(seed_), pid(pid_), iter(iter_), purpose(purpose_), k(0), spare(0.0), have(false), coop(coop_), buf_block(-1),
-        buf_uniform(false), b0(0.0), b1(0.0), out(nullptr), out_stride(0), out_n(0) {}
+        buf_uniform(false), b0(0.0), b1(0.0), fbuf_block(-1),
+        fbuf_uniform(false), fb0(0.f), fb1(0.f), fb2(0.f), fb3(0.f), out(nullptr), out_stride(0), out_n(0) {}
   __device__ __forceinline__ void set_outputs(double *out_, long long stride_, long long n_) {
     out = out_;
     out_stride = stride_;
@@ -484,6 +664,42 @@ struct NormalStream {
   __device__ __forceinline__ void for_pairs(const int n, F &&f) {
     if (coop == 0) { for_pairs_lane(n, f); return; }
     for_pairs_plain(n, f);
+  }
+  // ---- binary32 draws (namespace f32 above): each call consumes WHOLE blocks of the same stream and the same counter k, so they
+  // mix freely with pair(), uniform_pair(), while_events and the count draws.  |z| <= 6.7637.
+  // four N(0,1) from one block: (z0, z1) from its words (x, y), (z2, z3) from (z, w)
+  __device__ __forceinline__ void quad_f32(float &z0, float &z1, float &z2, float &z3) {
+    if (coop == 4) { fetch_f32<4>(k++, false, z0, z1, z2, z3); return; }
+    if (coop == 16) { fetch_f32<16>(k++, false, z0, z1, z2, z3); return; }
+    f32::box_muller_quad(stream_block(seed, pid, purpose, iter, k++), z0, z1, z2, z3);
+  }
+  // four U(0,1) from one block: u_i = ((w_i >> 9) + 1/2) 2^-23, exact, in (0, 1)
+  __device__ __forceinline__ void uniform_quad_f32(float &u0, float &u1, float &u2, float &u3) {
+    if (coop == 4) { fetch_f32<4>(k++, true, u0, u1, u2, u3); return; }
+    if (coop == 16) { fetch_f32<16>(k++, true, u0, u1, u2, u3); return; }
+    f32::uniform_quad(stream_block(seed, pid, purpose, iter, k++), u0, u1, u2, u3);
+  }
+  // f(z0, z1, z2, z3) for the next n blocks of the stream, in stream order: the loop to draw the bulk of binary32 normals with
+  template <class F>
+  __device__ __forceinline__ void for_quads_f32(const int n, F &&f) {
+    if (coop == 4) { for_quads_team<4>(n, f); return; }
+    if (coop == 16) { for_quads_team<16>(n, f); return; }
+    if (coop == 0) {                                     // a lane per particle: the re-spelled block generator (namespace loop)
+      f32::tables_f32_fill();                            // ... and the tables in binary32, converted once per call
+#pragma unroll kSimUnroll
+      for (int i = 0; i < n; ++i) {
+        float z0, z1, z2, z3;
+        f32::box_muller_quad<true>(loop::stream_block(seed, pid, purpose, iter, k++), z0, z1, z2, z3);
+        f(z0, z1, z2, z3);
+      }
+      return;
+    }
+#pragma unroll kSimUnroll
+    for (int i = 0; i < n; ++i) {                        // kCoopPlainLoop
+      float z0, z1, z2, z3;
+      quad_f32(z0, z1, z2, z3);
+      f(z0, z1, z2, z3);
+    }
   }
   __device__ __forceinline__ double next() {
     if (have) { have = false; return spare; }
@@ -699,6 +915,65 @@ struct NormalStream {
     else if (r > W) tail<W, 2>(c, r, f);
     else if (r > 0) tail<W, 1>(c, r, f);
     k += (uint32_t)n;
+  }
+  // ---- binary32 draws, a team per particle: for_pairs_team's scheme with four floats per block
+  template <int W, class F, int... J>
+  __device__ __forceinline__ void hand_out_f32(const float (&g)[4], F &f, lane_seq<J...>) {
+    (f(team_pick_ct_f32<W, J>(g[0]), team_pick_ct_f32<W, J>(g[1]), team_pick_ct_f32<W, J>(g[2]), team_pick_ct_f32<W, J>(g[3])), ...);
+  }
+  template <int W, class F, int... J>
+  __device__ __forceinline__ void hand_out_first_f32(const int m, const float (&g)[4], F &f, lane_seq<J...>) {   // the first m <= W blocks
+    ((J < m ? f(team_pick_ct_f32<W, J>(g[0]), team_pick_ct_f32<W, J>(g[1]), team_pick_ct_f32<W, J>(g[2]), team_pick_ct_f32<W, J>(g[3])) : (void)0), ...);
+  }
+  template <int W, int NB, class F>
+  __device__ __forceinline__ void tail_f32(const int c, const int r, F &f) {      // (NB - 1) W < r <= NB W blocks from block k + c on
+    using lanes = typename make_lane_seq<W>::type;
+    const uint32_t q = threadIdx.x & (uint32_t)(W - 1);
+    float g[NB][4];
+#pragma unroll
+    for (int a = 0; a < NB; ++a)
+      f32::box_muller_quad(stream_block(seed, pid, purpose, iter, k + (uint32_t)(c + W * a) + q), g[a][0], g[a][1], g[a][2], g[a][3]);
+#pragma unroll
+    for (int a = 0; a < NB - 1; ++a) hand_out_f32<W>(g[a], f, lanes{});
+    hand_out_first_f32<W>(r - (NB - 1) * W, g[NB - 1], f, lanes{});
+  }
+  template <int W, class F>
+  __device__ __forceinline__ void for_quads_team(const int n, F &f) {
+    using lanes = typename make_lane_seq<W>::type;
+    const uint32_t q = threadIdx.x & (uint32_t)(W - 1);
+    int c = 0;
+    for (; c + 4 * W <= n; c += 4 * W) {               // whole groups of 4 W: blocks k + c + W a + q, a = 0..3, on lane q
+      float g[4][4];
+#pragma unroll
+      for (int a = 0; a < 4; ++a)
+        f32::box_muller_quad(stream_block(seed, pid, purpose, iter, k + (uint32_t)(c + W * a) + q), g[a][0], g[a][1], g[a][2], g[a][3]);
+      hand_out_f32<W>(g[0], f, lanes{});
+      hand_out_f32<W>(g[1], f, lanes{});
+      hand_out_f32<W>(g[2], f, lanes{});
+      hand_out_f32<W>(g[3], f, lanes{});
+    }
+    const int r = n - c;                               // the rest, < 4 W blocks
+    if (r > 3 * W) tail_f32<W, 4>(c, r, f);
+    else if (r > 2 * W) tail_f32<W, 3>(c, r, f);
+    else if (r > W) tail_f32<W, 2>(c, r, f);
+    else if (r > 0) tail_f32<W, 1>(c, r, f);
+    k += (uint32_t)n;
+  }
+  // fetch for the binary32 draws: the group's blocks as four normals or four uniforms per lane
+  template <int W>
+  __device__ __forceinline__ void fetch_f32(uint32_t kk, bool uniform, float &x0, float &x1, float &x2, float &x3) {
+    const int base = (int)(kk & ~(uint32_t)(W - 1));
+    if (fbuf_block != base || fbuf_uniform != uniform) {
+      const u32x4 w = stream_block(seed, pid, purpose, iter, (uint32_t)base + (threadIdx.x & (uint32_t)(W - 1)));
+      if (uniform) f32::uniform_quad(w, fb0, fb1, fb2, fb3);
+      else f32::box_muller_quad(w, fb0, fb1, fb2, fb3);
+      fbuf_block = base;
+      fbuf_uniform = uniform;
+    }
+    x0 = team_pick_f32<W>(fb0, kk);
+    x1 = team_pick_f32<W>(fb1, kk);
+    x2 = team_pick_f32<W>(fb2, kk);
+    x3 = team_pick_f32<W>(fb3, kk);
   }
   // coop: block kk of the stream, from the lane of the team that holds it; a group of W blocks is (re)generated -- one block
   // per lane -- when the request leaves the buffered group or asks for the other kind (a simulator that mixes pair() and

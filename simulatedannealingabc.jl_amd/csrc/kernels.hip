@@ -609,6 +609,19 @@ int launch_rng_peak(uint64_t seed, int pairs, int64_t n, double *out, hipStream_
   return SABC_LAUNCH_RC();
 }
 
+int launch_normal_quads_f32(uint64_t seed, uint64_t pid0, uint32_t purpose, uint64_t iter, uint32_t k, int64_t m, float *out,
+                            hipStream_t stream) {
+  if (m <= 0) return 0;
+  hipLaunchKernelGGL(k_normal_quads_f32, dim3((unsigned)n_blocks(m)), dim3(kBlock), 0, stream, seed, pid0, purpose, iter, k, m, out);
+  return SABC_LAUNCH_RC();
+}
+
+int launch_rng_peak_f32(uint64_t seed, int quads, int64_t n, float *out, hipStream_t stream) {
+  if (n <= 0) return 0;
+  hipLaunchKernelGGL(k_rng_peak_f32, dim3((unsigned)n_blocks(n)), dim3(kBlock), 0, stream, seed, quads, n, out);
+  return SABC_LAUNCH_RC();
+}
+
 int launch_philox_debug(uint64_t seed, uint64_t pid, uint32_t purpose, uint64_t iter, uint32_t k, uint32_t *words,
                         double *normals, hipStream_t stream) {
   hipLaunchKernelGGL(k_philox_debug, dim3(1), dim3(64), 0, stream, seed, pid, purpose, iter, k, words, normals);

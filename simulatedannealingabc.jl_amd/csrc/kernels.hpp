@@ -260,6 +260,9 @@ int launch_prior_op(const ModelDesc &m, uint64_t pid0, int64_t n, double *theta,
 int launch_normal_pairs(uint64_t seed, uint64_t pid0, uint32_t purpose, uint64_t iter, uint32_t k, int64_t m, double *out,
                         hipStream_t stream);
 int launch_rng_peak(uint64_t seed, int pairs, int64_t n, double *out, hipStream_t stream);
+int launch_normal_quads_f32(uint64_t seed, uint64_t pid0, uint32_t purpose, uint64_t iter, uint32_t k, int64_t m, float *out,
+                            hipStream_t stream);
+int launch_rng_peak_f32(uint64_t seed, int quads, int64_t n, float *out, hipStream_t stream);
 int launch_philox_debug(uint64_t seed, uint64_t pid, uint32_t purpose, uint64_t iter, uint32_t k, uint32_t *words,
                         double *normals, hipStream_t stream);
 

@@ -75,4 +75,35 @@ k_normal_pairs(uint64_t seed, uint64_t pid0, uint32_t purpose, uint64_t iter, ui
   out[2 * i + 1] = z1;
 }
 
+// the binary32 twins: the four normals of block k per particle (sabc_op_normal_quads_f32) ...
+__global__ void __launch_bounds__(kBlock)
+k_normal_quads_f32(uint64_t seed, uint64_t pid0, uint32_t purpose, uint64_t iter, uint32_t k, int64_t m, float *out) {
+  rng_tables_init();
+  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (i >= m) return;
+  float z0, z1, z2, z3;
+  f32::box_muller_quad(stream_block(seed, pid0 + (uint64_t)i, purpose, iter, k), z0, z1, z2, z3);
+  out[4 * i] = z0;
+  out[4 * i + 1] = z1;
+  out[4 * i + 2] = z2;
+  out[4 * i + 3] = z3;
+}
+
+// ... and the bare loop of for_quads_f32, `quads` blocks of four normals per lane (sabc_op_rng_peak_f32)
+__global__ void __launch_bounds__(kBlock)
+k_rng_peak_f32(const uint64_t seed, const int quads, const int64_t n, float *__restrict__ out) {
+  rng_tables_init();
+  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (i >= n) return;
+  float acc = 0.0f;
+  NormalStream ns(seed, (uint64_t)i, PURPOSE_SIM, 0);
+  ns.for_quads_f32(quads, [&](const float z0, const float z1, const float z2, const float z3) {
+    acc += z0;
+    acc += z1;
+    acc += z2;
+    acc += z3;
+  });
+  out[i] = acc;
+}
+
 }  // namespace sabc

@@ -493,6 +493,16 @@ def op_normal_pairs(seed, pid0, m, purpose=1, it=0, k=0, device=0):
     return out
 
 
+def op_normal_quads_f32(seed, pid0, m, purpose=1, it=0, k=0, device=0):
+    """The four binary32 normals of block k for particles pid0..pid0+m-1: float32[m, 4]."""
+    out = np.empty((int(m), 4), dtype=np.float32)
+    rc = _lib.lib().sabc_op_normal_quads_f32(device, int(seed), int(pid0), int(purpose), int(it), int(k), int(m),
+                                             out.ctypes.data_as(C.POINTER(C.c_float)))
+    if rc:
+        raise SABCError(rc, _lib.global_error())
+    return out
+
+
 def rccl_unique_id():
     """ncclGetUniqueId through the library's own RCCL binding (rank 0 calls it, then broadcasts)."""
     buf = C.create_string_buffer(128)
@@ -506,6 +516,15 @@ def op_rng_peak(n_lanes=1_000_000, pairs_per_lane=50, repeats=20, device=0):
     """normals/s of the bare Philox + Box-Muller loop on this GPU (the VALU ceiling of the simulators)."""
     out = C.c_double()
     rc = _lib.lib().sabc_op_rng_peak(device, int(n_lanes), int(pairs_per_lane), int(repeats), C.byref(out))
+    if rc:
+        raise SABCError(rc, _lib.global_error())
+    return out.value
+
+
+def op_rng_peak_f32(n_lanes=1_000_000, quads_per_lane=25, repeats=20, device=0):
+    """normals/s of the bare loop of NormalStream::for_quads_f32 (Philox + four binary32 normals per block) on this GPU."""
+    out = C.c_double()
+    rc = _lib.lib().sabc_op_rng_peak_f32(device, int(n_lanes), int(quads_per_lane), int(repeats), C.byref(out))
     if rc:
         raise SABCError(rc, _lib.global_error())
     return out.value

@@ -20,7 +20,7 @@ import Dates
 import Base: show
 
 export sabc, update_population!, RandomWalk, DifferentialEvolution, StretchMove,
-       DeviceDistance, GaussianIID, Gaussian2D, GandK, LotkaVolterra, DeviceSource, StochasticSIR, NormalMoments, StochasticSIRSeries, SourcePrior,
+       DeviceDistance, GaussianIID, Gaussian2D, GandK, LotkaVolterra, DeviceSource, StochasticSIR, LotkaVolterraF32, NormalMoments, StochasticSIRSeries, SourcePrior,
        comm_unique_id, simulate_outputs, posterior_predictive
 
 const libsabc = get(ENV, "SABC_HIP_LIB", joinpath(@__DIR__, "..", "libsabc_hip.so"))
@@ -224,6 +224,20 @@ function StochasticSIR(data_obs; t_max=160.0, n_stats::Integer=3, compartments..
     text = read(joinpath(@__DIR__, "..", "device_sources", "sir.hip"), String)
     obs = Float64[data_obs.total_infected, data_obs.peak_infected, data_obs.t_peak]
     DeviceSource("#define SIR_N_STATS $(n_stats)\n" * text, 2, Int(n_stats), Float64[s0, i0, r0, t_max, obs...])
+end
+"""
+    LotkaVolterraF32(; n_steps=256, dt=0.05, σ=0.1, x0=50.0, y0=50.0, obs=(0.0, 0.0, 0.0, 0.0), n_stats=4)
+
+`LotkaVolterra` -- the same factored Euler–Maruyama step and statistics -- with its noise, state and step in binary32: a
+`DeviceSource` of device_sources/lotka_volterra_f32.hip, two steps per Philox block through `rng.for_quads_f32`.  θ, params and ρ
+stay Float64.
+"""
+function LotkaVolterraF32(; n_steps::Integer=256, dt=0.05, σ=0.1, x0=50.0, y0=50.0, obs=(0.0, 0.0, 0.0, 0.0), n_stats::Integer=4)
+    n_steps >= 2 || throw(ArgumentError("n_steps must be at least 2"))
+    n_stats in 1:4 || throw(ArgumentError("n_stats is 1..4"))
+    length(obs) == 4 || throw(ArgumentError("obs holds (mean X, sd X, mean Y, sd Y)"))
+    text = read(joinpath(@__DIR__, "..", "device_sources", "lotka_volterra_f32.hip"), String)
+    DeviceSource("#define LV_N_STATS $(n_stats)\n" * text, 3, Int(n_stats), Float64[n_steps, dt, σ, x0, y0, obs...])
 end
 """
     NormalMoments(; y_obs=nothing)

@@ -172,6 +172,13 @@ class DeviceSource(DeviceDistance):
     the same fused propose -> simulate -> ECDF -> accept kernel as the built-in simulators.  n_stats <= 64 (_lib.MAX_SOURCE_STATS;
     above 16 the wide form of the kernels).  `params` holds at most 32 values.
 
+    Binary32 draws, for simulators whose noise needs no more: `rng.quad_f32(z0, z1, z2, z3)` four N(0,1) floats from one block
+    ((z0, z1) from its first two words, (z2, z3) from the others; |z| <= sqrt(66 ln 2) = 6.7637, the f64 draws reach 8.57),
+    `rng.uniform_quad_f32(u0, u1, u2, u3)` four U(0,1) floats ((w >> 9) + 1/2) 2^-23, and
+    `rng.for_quads_f32(n, [&](float z0, float z1, float z2, float z3) { ... })` the next n blocks in stream order -- the loop to
+    draw the bulk with: half the generator's instructions per normal.  They consume whole blocks of the same stream and mix freely
+    with the f64 draws.  `theta`, `params`, `rho_out`, `sabc::data_at` and `sabc::emit` stay `double`.
+
     Observations the simulator compares against (a time series) are `data`: one array-like, or a sequence of array-likes -- one
     segment each, at most 8 --, float64, flattened in C order and kept in device memory by the handle.  The source -- the
     simulator and, with a SourcePrior, the prior -- reads them with `sabc::data_len(segment = 0)`, `sabc::data_at(i, segment = 0)`
@@ -325,6 +332,27 @@ class StochasticSIR(DeviceSource):
         model = cls((0.0, 0.0, 0.0), S0=S0, I0=I0, R0=R0, t_max=t_max)
         out = simulate_outputs(model, np.asarray(theta, dtype=np.float64).reshape(1, 2), seed=seed, device=device)[0, 0]
         return {name: float(v) for name, v in zip(model.output_names, out)}
+
+
+class LotkaVolterraF32(DeviceSource):
+    """`LotkaVolterra` -- the same factored Euler-Maruyama step, the same four statistics -- with its noise, state and step
+    in binary32, as HIP source (device_sources/lotka_volterra_f32.hip): two steps per Philox block through
+    `rng.for_quads_f32`, about half the generator's instructions per normal of the f64 model.  For simulators whose noise is
+    binary32-grade anyway (an SDE path compared at 1e-2); theta, params and rho stay float64, and the running sums are sums of
+    deviations from (x0, y0), finished in float64.  n_stats = 1..4: the first so many of |mean X, sd X, mean Y, sd Y - obs|.
+    Outputs: the two paths, X at 0..n_steps-1 and Y behind it (`posterior_predictive` gives [n, n_rep, 2 n_steps])."""
+
+    def __init__(self, n_steps=256, dt=0.05, σ=0.1, x0=50.0, y0=50.0, obs=(0.0, 0.0, 0.0, 0.0), n_stats=4):
+        if isinstance(n_steps, bool) or int(n_steps) != n_steps or int(n_steps) < 2:
+            raise ValueError(f"n_steps must be an integer of at least 2 (the standard deviations divide by n_steps - 1), got {n_steps!r}")
+        if int(n_stats) not in (1, 2, 3, 4):
+            raise ValueError("n_stats is 1..4")
+        self.n_steps, self.dt, self.σ, self.x0, self.y0 = int(n_steps), float(dt), float(σ), float(x0), float(y0)
+        self.obs = tuple(float(o) for o in obs)
+        if len(self.obs) != 4:
+            raise ValueError("obs holds (mean X, sd X, mean Y, sd Y)")
+        super().__init__(f"#define LV_N_STATS {int(n_stats)}\n" + device_source_text("lotka_volterra_f32"), 3, int(n_stats),
+                         [self.n_steps, self.dt, self.σ, self.x0, self.y0, *self.obs], n_outputs=2 * self.n_steps)
 
 
 class NormalMoments(DeviceSource):
