@@ -247,6 +247,16 @@ SABC_API int64_t     sabc_host_callback_calls(const sabc_handle *h);
    emit does nothing when not emitting and ignores an i outside [0, n_outputs) -- this index IS checked.  An output that is never
    emitted (a simulation may stop early) reads as NaN.  Population updates never emit: there every emit, and every block under
    `if (sabc::emitting(rng))`, is dead code the compiler removes.  sabc_op_simulate_outputs below is the forward run.
+   ORDER STATISTICS of a simulated sample (quantiles: the summaries to reach for where moments are poor ones), csrc/sort_network.hpp:
+       template <int N> void sabc::sort_ascending(double (&x)[N]);      N a compile-time constant: up to 32 the network unrolled
+       void   sabc::sort_ascending(double *x, int n);                   any n >= 0, loops; float twins of both
+       double sabc::order_statistic(const double *sorted, int n, int rank);     1-based; +inf for a rank outside [1, n]
+       double sabc::quantile(const double *sorted, int n, double p);    Julia's default (type 7; NumPy's "linear"), p clamped to [0, 1]
+   The sort is a data-oblivious network (Batcher's odd-even merge sort; a compare-exchange is one min and one max, never a
+   branch): which elements meet depends on n alone, so the lanes of a wave index their arrays alike and a lane, a quad or a row
+   of lanes per particle return the same bits -- a sorted array is unique.  A NaN enters as +inf (the built-in g-and-k model's
+   policy) and comes out last; -0.0 and +0.0 compare equal.  Do not write a sort of your own in the source: a data-dependent loop
+   diverges across the wave.  In the one-launch form every lane of a team sorts the whole sample (no cooperative form yet).
    It is compiled with hipRTC for gfx950 against csrc/update_kernel.hpp -- the same propose -> simulate -> ECDF -> accept
    kernel, reductions and Philox streams as the built-in simulators -- and must be registered before sabc_initialize.
    On failure sabc_last_error(h) holds the compiler log. */

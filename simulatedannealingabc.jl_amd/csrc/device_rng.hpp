@@ -13,6 +13,7 @@
 #ifndef INFINITY                 // hipRTC has no <math.h>
 #define INFINITY (__builtin_huge_val())
 #endif
+#include "sort_network.hpp"      // sabc::sort_ascending / order_statistic / quantile: part of what a simulator from source sees
 
 namespace sabc {
 

@@ -20,7 +20,7 @@ import Dates
 import Base: show
 
 export sabc, update_population!, RandomWalk, DifferentialEvolution, StretchMove,
-       DeviceDistance, GaussianIID, Gaussian2D, GandK, LotkaVolterra, DeviceSource, StochasticSIR, LotkaVolterraF32, NormalMoments, StochasticSIRSeries, SourcePrior,
+       DeviceDistance, GaussianIID, Gaussian2D, GandK, LotkaVolterra, DeviceSource, StochasticSIR, LotkaVolterraF32, NormalMoments, StochasticSIRSeries, GandKQuantiles, SourcePrior,
        comm_unique_id, simulate_outputs, posterior_predictive
 
 const libsabc = get(ENV, "SABC_HIP_LIB", joinpath(@__DIR__, "..", "libsabc_hip.so"))
@@ -272,6 +272,36 @@ end
 # the source reads I_obs[k] for every k < length(t_obs): a shorter I_obs would be read past its end
 check_series_data(segs) = (length(segs) == 2 && length(segs[1]) == length(segs[2]) >= 1 && issorted(segs[1]; lt=<=)) ||
     throw(ArgumentError("t_obs is increasing, holds at least one value and is as long as I_obs"))
+
+"""
+    GandKQuantiles(probs, q_obs; n_draws=128, c=0.8)
+    GandKQuantiles(y_obs; probs=(1:7) ./ 8, n_draws=length(y_obs), c=0.8)
+
+g-and-k, θ = (A, B, g, k), with any number of draws and any set of quantiles: ρ_j = |quantile(x_sim, probs[j]) − q_obs[j]| with
+Julia's default `quantile`.  Two data segments, `probs` and `q_obs` (1 to 16 values each); the second method takes `q_obs`
+from a sample.  A `DeviceSource` of device_sources/gk_quantiles.hip, which sorts the draws with `sabc::sort_ascending`.
+"""
+function GandKQuantiles(probs, q_obs; n_draws::Integer=128, c=0.8)
+    2 <= n_draws <= 1024 || throw(ArgumentError("n_draws must be in 2..1024"))
+    1 <= length(probs) <= 16 || throw(ArgumentError("1 to 16 quantiles"))
+    text = read(joinpath(@__DIR__, "..", "device_sources", "gk_quantiles.hip"), String)
+    n_q = length(probs)
+    DeviceSource("#define GKQ_N_DRAWS $(n_draws)\n#define GKQ_N_STATS $(n_q)\n" * text, 4, n_q; params=Float64[n_draws, c],
+                 data=(probs, q_obs), data_names=(:probs, :q_obs), validate=segs -> check_quantile_data(segs, n_q))
+end
+GandKQuantiles(y_obs; probs=(1:7) ./ 8, n_draws::Integer=length(y_obs), c=0.8) =
+    GandKQuantiles(probs, type7_quantiles(sort(data_segment(y_obs)), probs); n_draws=n_draws, c=c)
+# Julia's default quantile (Statistics.quantile, type 7) of an ascending vector, without the dependency
+function type7_quantiles(x, probs)
+    map(probs) do p
+        h = (length(x) - 1) * clamp(p, 0.0, 1.0)
+        i = floor(Int, h)
+        i >= length(x) - 1 ? x[end] : x[i + 1] + (h - i) * (x[i + 2] - x[i + 1])
+    end
+end
+# the source reads probs[j] and q_obs[j] and writes ρ[j] for every j < n_stats
+check_quantile_data(segs, n_q) = (length(segs) == 2 && length(segs[1]) == length(segs[2]) == n_q && all(p -> 0 <= p <= 1, segs[1])) ||
+    throw(ArgumentError("probs and q_obs hold $(n_q) values each, every probability in [0, 1]"))
 """
     SourcePrior(d)
 

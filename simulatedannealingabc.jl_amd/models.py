@@ -194,7 +194,18 @@ class DeviceSource(DeviceDistance):
     many).  Population updates never emit -- the calls are dead code there --; `simulate_outputs`, `posterior_predictive` and
     `SabcHandle.simulate_outputs` run the source forward and return what it emitted, NaN where it emitted nothing.  `n_outputs`
     declares how many there are: an int, or a callable of the data segments (a series model emits one value per observation
-    time); None: the model declares no outputs.  `output_names` names them (then n_outputs may be left out)."""
+    time); None: the model declares no outputs.  `output_names` names them (then n_outputs may be left out).
+
+    Order statistics of a simulated sample (csrc/sort_network.hpp): `sabc::sort_ascending(x)` for `double x[N]` with N a
+    compile-time constant (up to 32 the sorting network unrolled, on registers where the array's other indices are constants
+    too), `sabc::sort_ascending(x, n)` for any n >= 0 (loops), float twins of both, `sabc::order_statistic(sorted, n, rank)`
+    (1-based; +inf outside [1, n]) and `sabc::quantile(sorted, n, p)` (Julia's default, type 7; NumPy's "linear"; p clamped to
+    [0, 1]).  The sort is a data-oblivious network -- Batcher's odd-even merge sort, a compare-exchange being one min and one
+    max, never a branch --: which elements meet depends on n alone, so the lanes of a wave index their arrays alike, and a
+    lane, a quad or a row of lanes per particle return the same bits (a sorted array is unique).  A NaN enters as +inf, the
+    built-in g-and-k model's policy, and comes out last; -0.0 and +0.0 compare equal.  A sort written by hand in the source is a
+    data-dependent loop that diverges across the wave.  In the one-launch form every lane of a team sorts the whole sample (there
+    is no cooperative form yet).  `GandKQuantiles` is the shipped model on it."""
     model_id = _lib.MODEL_USER
 
     def __init__(self, hip_source: str, n_para: int, n_stats: int, params=(), data=None, data_names=None, n_outputs=None,
@@ -419,3 +430,46 @@ class StochasticSIRSeries(DeviceSource):
             raise ValueError("t_obs and I_obs hold the same number of values, at least one")
         if np.any(np.diff(segments[0]) <= 0):
             raise ValueError("t_obs must be increasing")
+
+
+class GandKQuantiles(DeviceSource):
+    """g-and-k -- x = A + B (1 + c tanh(g z / 2)) (1 + z^2)^k z, theta = (A, B, g, k) -- with real data shapes: any number of draws
+    and any set of quantiles, where the built-in `GandK` sorts 128 draws at four ranks inside a kernel of its own.
+    rho_j = |quantile(sort(x_1..n_draws), probs[j]) - q_obs[j]|, the quantile Julia's default (type 7; NumPy's "linear").
+    `probs` and `q_obs` are two data segments (1 to 16 values each, as many as the model has statistics; another set of as
+    many quantiles is another `SabcHandle.set_data` or `sabc(model, prior, probs=..., q_obs=...)`, never another compilation);
+    `n_draws` and `c` are params.  `from_observations(y_obs)` takes `q_obs` from a sample with `np.quantile`.
+    Source: device_sources/gk_quantiles.hip, which sorts the draws with `sabc::sort_ascending` -- n_draws is a compile-time constant
+    of the source, up to 32 draws the sorting network runs on registers.  Outputs: the sorted sample (`posterior_predictive`
+    gives [n, n_rep, n_draws], ascending along the last axis)."""
+    MAX_QUANTILES = 16
+    MAX_DRAWS = 1024                 # the sample is 8 n_draws bytes of private memory per lane
+    OCTILES = tuple(j / 8 for j in range(1, 8))
+
+    def __init__(self, probs, q_obs, n_draws=128, c=0.8, data_names=("probs", "q_obs")):
+        if isinstance(n_draws, bool) or int(n_draws) != n_draws or not 2 <= int(n_draws) <= self.MAX_DRAWS:
+            raise ValueError(f"n_draws must be an integer in 2..{self.MAX_DRAWS}, got {n_draws!r}")
+        probs, q_obs = _segment(probs), _segment(q_obs)
+        if not 1 <= len(probs) <= self.MAX_QUANTILES:
+            raise ValueError(f"1 to {self.MAX_QUANTILES} quantiles, got {len(probs)}")
+        self.n_draws, self.c = int(n_draws), float(c)
+        super().__init__(f"#define GKQ_N_DRAWS {self.n_draws}\n#define GKQ_N_STATS {len(probs)}\n" + device_source_text("gk_quantiles"),
+                         4, len(probs), [self.n_draws, self.c], data=[probs, q_obs], data_names=data_names, n_outputs=self.n_draws)
+
+    @classmethod
+    def from_observations(cls, y_obs, probs=OCTILES, n_draws=None, c=0.8):
+        """The model for a sample `y_obs`: q_obs = np.quantile(y_obs, probs) and, unless given, as many draws per simulation as
+        there are observations."""
+        y_obs = _segment(y_obs)
+        return cls(probs, np.quantile(y_obs, _segment(probs)), n_draws=len(y_obs) if n_draws is None else n_draws, c=c)
+
+    def validate_data(self, segments):
+        # the source reads probs[j] and q_obs[j] and writes rho[j] for every j < n_stats
+        if len(segments) != 2 or len(segments[0]) != len(segments[1]):
+            raise ValueError("probs and q_obs hold the same number of values")
+        if not 1 <= len(segments[0]) <= self.MAX_QUANTILES:
+            raise ValueError(f"1 to {self.MAX_QUANTILES} quantiles, got {len(segments[0])}")
+        if len(segments[0]) != self.n_stats:
+            raise ValueError(f"this model was made for {self.n_stats} quantiles (its n_stats), got {len(segments[0])}")
+        if not np.all((segments[0] >= 0.0) & (segments[0] <= 1.0)):
+            raise ValueError("probs are probabilities: every value in [0, 1]")
