@@ -256,11 +256,39 @@ SABC_API int64_t     sabc_host_callback_calls(const sabc_handle *h);
    branch): which elements meet depends on n alone, so the lanes of a wave index their arrays alike and a lane, a quad or a row
    of lanes per particle return the same bits -- a sorted array is unique.  A NaN enters as +inf (the built-in g-and-k model's
    policy) and comes out last; -0.0 and +0.0 compare equal.  Do not write a sort of your own in the source: a data-dependent loop
-   diverges across the wave.  In the one-launch form every lane of a team sorts the whole sample (no cooperative form yet).
+   diverges across the wave.  With this entry point every lane of a team sorts the whole sample; the cooperative form is the
+   team-aware entry point below.
    It is compiled with hipRTC for gfx950 against csrc/update_kernel.hpp -- the same propose -> simulate -> ECDF -> accept
    kernel, reductions and Philox streams as the built-in simulators -- and must be registered before sabc_initialize.
    On failure sabc_last_error(h) holds the compiler log. */
 SABC_API int         sabc_register_device_simulator(sabc_handle *h, const char *hip_source);
+/* A TEAM-AWARE simulator: a sample spread over the lanes that run one particle, drawn and sorted by them together
+   (csrc/team_sample.hpp).  `hip_source` defines, instead of sabc_user_simulate,
+       template <int W>      // 1, 4 or 16: the lanes that run this particle side by side
+       __device__ void sabc_user_simulate_team(const double *theta, const double *params, sabc::NormalStream &rng, double *rho_out);
+   All lanes of a team see the same data and must make the same requests -- of rng and of a Sample -- in the same order.
+       sabc::Sample<N, W> x;           N >= 1 doubles of this particle, N a compile-time constant; lane q of the team holds
+                                       M = pow2ceil(2 ceil(ceil(N / 2) / W)) of them in registers, pad slots +inf
+       x.fill_normals(rng, f);         element i = f(z_i), z_i the next N normals of the stream in stream order: ceil(N / 2) whole
+                                       blocks, the second normal of an odd last block dropped; every lane generates its own
+                                       blocks (block b on lane b mod W) and applies f to its own normals only
+       x.fill(g);                      element i = g(i)
+       x.drawn(i);                     before the sort: element i
+       x.sort();                       ascending; a bitonic network on W M slots -- min and max between two registers of a lane, DPP
+                                       or ds_swizzle between lanes; no LDS memory, no barrier.  A NaN enters as +inf at fill time
+       x.at(i); x.order_statistic(rank); x.quantile(p);      after the sort: rank i (0-based); 1-based, +inf outside [1, N]; type 7
+       x.emit(rng, first_output);      element r of the current order (draw order before the sort, rank order after) to output
+                                       first_output + r, each value written once
+   Every read-out returns the same value on every lane of the team; a rank known only at run time must be uniform over the team.
+   Limits: W = 1, or more than 32 slots per lane (N > 32 W): every lane holds all N values and sorts them with
+   sabc::sort_ascending, what a lane per particle costs -- any N compiles for every W.  doubles only.  n_stats <= 16: the
+   kernels for 16 < n_stats <= 64 run a lane per particle, and a team-aware registration there is SABC_ERR_BAD_CONFIG.
+   chain_lanes = 1 | 4 | 16: the lanes per particle on the launch chain (k_update_team) and in the forward run
+   (sabc_op_simulate, sabc_op_simulate_outputs); 1 runs the ordinary kernels with sabc_user_simulate_team<1>.  The one-launch
+   form of small populations keeps choosing its own team by fit (sabc_persistent_lanes); sabc_chain_team_lanes: chain_lanes
+   of the registered source, 0: not team-aware (or none registered). */
+SABC_API int         sabc_register_device_simulator_team(sabc_handle *h, const char *hip_source, int32_t chain_lanes);
+SABC_API int32_t     sabc_chain_team_lanes(const sabc_handle *h);
 /* SABC_MODEL_USER only: the observed data the source reads through sabc::data*().  `values`: n doubles, copied into device
    memory the handle owns; segment_len[0 .. n_segments) sums to n, n_segments <= SABC_MAX_DATA_SEGMENTS; n = 0 drops the data.
    Legal before or after sabc_register_device_simulator (registering again keeps the data) and between any two calls on an
@@ -278,6 +306,12 @@ SABC_API int         sabc_op_compile_device_simulator(const char *hip_source, in
 /* the same for a source that also carries the prior (prior_joint = 3) */
 SABC_API int         sabc_op_compile_device_simulator_with_prior(const char *hip_source, int32_t d, int32_t s, char *log_out,
                                                                  int64_t log_cap);
+/* ... for a team-aware source (sabc_register_device_simulator_team), without and with the prior (log_len an int64_t as
+   log_cap above: this header is also read by hipRTC, which has no <stddef.h>) */
+SABC_API int         sabc_op_compile_device_simulator_team(const char *hip_source, int32_t n_para, int32_t n_stats, char *log,
+                                                           int64_t log_len);
+SABC_API int         sabc_op_compile_device_simulator_team_with_prior(const char *hip_source, int32_t n_para, int32_t n_stats,
+                                                                      char *log, int64_t log_len);
 SABC_API int         sabc_comm_init_rccl(sabc_handle *h, const void *unique_id_128b);
 SABC_API int         sabc_comm_unique_id(void *out_128b);
 /* one allreduce + one allgather through the installed collectives, checked on the host */

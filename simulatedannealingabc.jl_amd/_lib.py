@@ -19,6 +19,7 @@ ABI_VERSION = 6
 P2P_DESC_BYTES, P2P_MAX_WORLD = 512, 8
 MAX_PARA, MAX_STATS, MAX_MODEL_PARAMS = 16, 64, 32
 MAX_SOURCE_STATS = 64     # simulators compiled from source (SABC_MODEL_USER)
+NARROW_STATS = 16         # ... above this many the wide form of their kernels (csrc/kernels.hpp: kNarrowStats), a lane per particle
 MAX_JOINT_PARA = 8
 MAX_DATA_SEGMENTS = 8     # observed data of a simulator from source (sabc_set_device_data)
 MODEL_HOST, MODEL_GAUSS_IID, MODEL_GAUSS2D, MODEL_GK, MODEL_LV, MODEL_USER = 0, 1, 2, 3, 4, 5
@@ -147,6 +148,10 @@ def bind(L, strict=True):
         "sabc_set_host_simulator": ([vp, SIMULATE_FN, vp], C.c_int),
         "sabc_set_host_prior": ([vp, PRIOR_SAMPLE_FN, PRIOR_LOGPDF_FN, vp], C.c_int),
         "sabc_register_device_simulator": ([vp, C.c_char_p], C.c_int),
+        "sabc_register_device_simulator_team": ([vp, C.c_char_p, C.c_int32], C.c_int),
+        "sabc_chain_team_lanes": ([vp], C.c_int32),
+        "sabc_op_compile_device_simulator_team": ([C.c_char_p, C.c_int32, C.c_int32, C.c_char_p, C.c_int64], C.c_int),
+        "sabc_op_compile_device_simulator_team_with_prior": ([C.c_char_p, C.c_int32, C.c_int32, C.c_char_p, C.c_int64], C.c_int),
         "sabc_set_device_data": ([vp, dp, C.c_int64, ip64, C.c_int32], C.c_int),
         "sabc_device_data_len": ([vp], C.c_int64),
         "sabc_op_compile_device_simulator": ([C.c_char_p, C.c_int32, C.c_int32, C.c_char_p, C.c_int64], C.c_int),

@@ -213,7 +213,7 @@ int sabc_set_stream(sabc_handle *h, void *hip_stream) {
   return h->be->set_stream((hipStream_t)hip_stream) ? hfail(h, SABC_ERR_HIP) : 0;
 }
 
-static int compile_only(const char *hip_source, int32_t d, int32_t s, char *log_out, int64_t log_cap, bool user_prior);
+static int compile_only(const char *hip_source, int32_t d, int32_t s, char *log_out, int64_t log_cap, bool user_prior, bool team_aware = false);
 
 int sabc_op_compile_device_simulator(const char *hip_source, int32_t d, int32_t s, char *log_out, int64_t log_cap) {
   return compile_only(hip_source, d, s, log_out, log_cap, false);
@@ -222,11 +222,18 @@ int sabc_op_compile_device_simulator_with_prior(const char *hip_source, int32_t 
   return compile_only(hip_source, d, s, log_out, log_cap, true);
 }
 
-static int compile_only(const char *hip_source, int32_t d, int32_t s, char *log_out, int64_t log_cap, bool user_prior) {
+int sabc_op_compile_device_simulator_team(const char *hip_source, int32_t d, int32_t s, char *log_out, int64_t log_cap) {
+  return compile_only(hip_source, d, s, log_out, log_cap, false, true);
+}
+int sabc_op_compile_device_simulator_team_with_prior(const char *hip_source, int32_t d, int32_t s, char *log_out, int64_t log_cap) {
+  return compile_only(hip_source, d, s, log_out, log_cap, true, true);
+}
+
+static int compile_only(const char *hip_source, int32_t d, int32_t s, char *log_out, int64_t log_cap, bool user_prior, bool team_aware) {
   if (!hip_source) { g_err = "null device simulator source"; return SABC_ERR_BAD_CONFIG; }
   std::string log;
   size_t cs = 0;
-  const RtcRequest rq{hip_source, d, s, rtc_default_csrc_dir(), user_prior, /*with_persistent=*/persistent_fits(d, s)};
+  const RtcRequest rq{hip_source, d, s, rtc_default_csrc_dir(), user_prior, /*with_persistent=*/persistent_fits(d, s), team_aware};
   const int rc = rtc_compile(rq, nullptr, &log, &cs);
   if (log_out && log_cap > 0) { std::snprintf(log_out, (size_t)log_cap, "%s", log.c_str()); }
   if (rc) { g_err = "compiling the device simulator failed:\n" + log; return SABC_ERR_BAD_CONFIG; }
@@ -240,6 +247,16 @@ int sabc_register_device_simulator(sabc_handle *h, const char *hip_source) {
   h->err.clear();
   return h->be->register_device_simulator(hip_source) ? hfail(h, SABC_ERR_BAD_CONFIG) : 0;
 }
+
+int sabc_register_device_simulator_team(sabc_handle *h, const char *hip_source, int32_t chain_lanes) {
+  if (!h || !hip_source) return hset(h, SABC_ERR_BAD_CONFIG, "null device simulator source");
+  if (h->eng->model().model_id != SABC_MODEL_USER) return hset(h, SABC_ERR_BAD_CONFIG, "the handle was not created with SABC_MODEL_USER");
+  if (chain_lanes != 1 && chain_lanes != 4 && chain_lanes != 16) return hset(h, SABC_ERR_BAD_CONFIG, "chain_lanes of a team-aware simulator is 1, 4 or 16");
+  if (int rc = enter(h)) return rc;
+  h->err.clear();
+  return h->be->register_device_simulator(hip_source, chain_lanes) ? hfail(h, SABC_ERR_BAD_CONFIG) : 0;
+}
+int32_t sabc_chain_team_lanes(const sabc_handle *h) { return h ? h->be->chain_team_lanes() : 0; }
 
 int sabc_set_device_data(sabc_handle *h, const double *values, int64_t n, const int64_t *segment_len, int32_t n_segments) {
   if (int rc = enter(h)) return rc;

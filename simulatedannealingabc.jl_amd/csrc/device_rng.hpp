@@ -1006,3 +1006,5 @@ __device__ __forceinline__ void emit(NormalStream &rng, const long long i, const
 }
 
 }  // namespace sabc
+
+#include "team_sample.hpp"     // sabc::Sample<N, W>: a sample spread over the lanes of a team (uses NormalStream, team_pick and emit above)

@@ -289,15 +289,21 @@ int HipBackend::profile_get(int kernel, double *total_ms, int64_t *launches) {
   return 0;
 }
 
-int HipBackend::register_device_simulator(const char *hip_source) {
+int HipBackend::register_device_simulator(const char *hip_source, int chain_lanes) {
   if (m_.model_id != SABC_MODEL_USER) { err_ = "the handle was not created with SABC_MODEL_USER"; return -1; }
+  const bool team_aware = chain_lanes != 0;
+  if (team_aware && chain_lanes != 1 && chain_lanes != 4 && chain_lanes != 16) { err_ = "chain_lanes of a team-aware simulator is 1, 4 or 16"; return -1; }
+  if (team_aware && source_wide(m_.s)) {
+    err_ = "a team-aware simulator (sabc_user_simulate_team<W>) has no wide form: n_stats <= 16 (the kernels for 16 < n_stats <= 64 run a lane per particle)";
+    return -1;
+  }
   HB_CHECK(hipSetDevice(device_), "hipSetDevice");
   if (stream_) HB_CHECK(hipStreamSynchronize(stream_), "hipStreamSynchronize");
   rtc_release(&rtc_);
   std::string log;
   // (the one-launch form of small shards -- k_update_persistent -- is compiled only for handles that can take it)
   const bool small = persist_.max > 0 && sh_.world == 1 && sh_.n_local <= persist_.max && persistent_fits(m_.d, m_.s);
-  RtcRequest rq{hip_source, m_.d, m_.s, rtc_default_csrc_dir(), /*user_prior=*/m_.prior_joint == 3, /*with_persistent=*/small};
+  RtcRequest rq{hip_source, m_.d, m_.s, rtc_default_csrc_dir(), /*user_prior=*/m_.prior_joint == 3, /*with_persistent=*/small, team_aware};
   if (rtc_compile(rq, &rtc_, &log)) {
     // the one-launch kernels are the largest of the unit (three team widths x three proposals): should the compiler give up on
     // them for this simulator, the launch chain alone still runs it -- only a source that fails there too is an error
@@ -308,6 +314,7 @@ int HipBackend::register_device_simulator(const char *hip_source) {
       return -1;
     }
   }
+  rtc_.chain_lanes = team_aware ? chain_lanes : 1;
   return push_data_desc();                                // a new module starts with an empty descriptor: the data are kept
 }
 

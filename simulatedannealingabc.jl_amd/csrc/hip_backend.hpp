@@ -33,7 +33,10 @@ class HipBackend : public Backend {
     return 0;
   }
   // SABC_MODEL_USER: compile the simulator source into the update kernels (rtc.hpp); the compiler log goes to error()
-  int register_device_simulator(const char *hip_source);
+  // chain_lanes = 0: the source defines sabc_user_simulate; 1 | 4 | 16: it is team-aware (sabc_user_simulate_team<W>) and runs
+  // with that many lanes per particle on the launch chain and in the forward run
+  int register_device_simulator(const char *hip_source, int chain_lanes = 0);
+  int chain_team_lanes() const { return rtc_.module && rtc_.team_aware ? rtc_.chain_lanes : 0; }
   // SABC_MODEL_USER: the observed data the source reads through sabc::data*() (rtc.hpp: RtcDataDesc).  0, or the SABC_ERR_*
   // code with the text in error(); on an error the old data stay in place
   int set_device_data(const double *values, int64_t n, const int64_t *segment_len, int32_t n_segments);

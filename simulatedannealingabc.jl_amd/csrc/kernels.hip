@@ -114,7 +114,8 @@ int launch_cdf_population(const ModelDesc &m, PopPtrs pp, CdfPtrs cdf, hipStream
   return SABC_LAUNCH_RC();
 }
 
-// workgroups (= partial rows) of one k_update launch over act_n particles
+// workgroups (= partial rows) of one k_update launch over act_n particles (k_update_team: the same number -- a workgroup takes
+// its particles in several trips, update_kernel.hpp)
 int64_t update_rows(const ModelDesc &m, int64_t act_n) {
   if (act_n <= 0) return 0;
   if (m.model_id == SABC_MODEL_USER && source_wide(m.s)) return source_blocks(m, act_n);   // k_update_wide
@@ -225,6 +226,11 @@ int launch_update(const ModelDesc &m, const StepArgs &c, const ControlBlock *cb,
   if (m.model_id == SABC_MODEL_USER) {
     if (!rtc || c.prop_kind < 0 || c.prop_kind > 2 || !rtc->update[c.prop_kind]) return (int)hipErrorInvalidValue;
     const unsigned b = source_wide(m.s) ? kWideBlock : update_block_threads(m.s);     // (k_update_wide | k_update)
+    if (rtc->team_aware && rtc->chain_lanes > 1) {   // k_update_team: the same rows, a workgroup's particles in chain_lanes trips
+      const hipFunction_t f = source_wide(m.s) ? nullptr : rtc->update_team[persist_team(rtc->chain_lanes) - 1][c.prop_kind];
+      if (!f) return (int)hipErrorInvalidValue;
+      return module_launch(f, grid.x, b, stream, ev0, ev1, m, c, cb, pp, cdf, pv, act_lo, act_n, out);
+    }
     return module_launch(rtc->update[c.prop_kind], grid.x, b, stream, ev0, ev1, m, c, cb, pp, cdf, pv, act_lo, act_n, out);
   }
   // ev0 / ev1 (optional): timing events attached to the dispatch packet itself (hipExtLaunchKernel), so that
@@ -566,6 +572,12 @@ int launch_simulate_batch(const ModelDesc &m, const double *theta, int64_t n, ui
   if (n <= 0) return 0;
   if (m.model_id == SABC_MODEL_USER) {
     if (!rtc || !rtc->simulate_batch) return (int)hipErrorInvalidValue;
+    if (rtc->team_aware && rtc->chain_lanes > 1) {   // k_simulate_batch_team: chain_lanes threads per row
+      const hipFunction_t f = source_wide(m.s) ? nullptr : rtc->simulate_batch_team[persist_team(rtc->chain_lanes) - 1];
+      if (!f) return (int)hipErrorInvalidValue;
+      return module_launch(f, (unsigned)n_blocks(n * rtc->chain_lanes), kBlock, stream, nullptr, nullptr, m, theta, n, pid0, iter, rho_out, gate,
+                           out, n_out, purpose);
+    }
     return module_launch(rtc->simulate_batch, source_blocks(m, n), source_block(m), stream, nullptr, nullptr, m, theta, n, pid0, iter,
                          rho_out, gate, out, n_out, purpose);
   }

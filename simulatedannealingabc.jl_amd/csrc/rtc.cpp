@@ -272,11 +272,48 @@ struct Sim<SABC_MODEL_USER, D, S> {
 }  // namespace sabc
 )SABC";
 
+// ---- a team-aware source (RtcRequest::team_aware): the entry point is a template over the lanes that run the particle ----
+// Declared in place of sabc_user_simulate, with the same attribute for the same reason; Sim dispatches on its coop, which is a
+// constant after inlining in every kernel (0 and kCoopPlainLoop: a lane per particle), so each kernel keeps one instantiation.
+const char kTeamDecl[] = R"SABC(
+template <int W>
+__device__ __attribute__((always_inline)) void sabc_user_simulate_team(const double *theta, const double *params,
+                                                                       sabc::NormalStream &rng, double *rho_out);
+)SABC";
+
+const char kTeamSimTail[] = R"SABC(
+namespace sabc {
+template <int D, int S>
+struct Sim<SABC_MODEL_USER, D, S> {
+  static __device__ __forceinline__ void dispatch(const double *th, const double *p, NormalStream &ns, double *rho) {
+    if (ns.coop == 16) ::sabc_user_simulate_team<16>(th, p, ns, rho);
+    else if (ns.coop == 4) ::sabc_user_simulate_team<4>(th, p, ns, rho);
+    else ::sabc_user_simulate_team<1>(th, p, ns, rho);
+  }
+  static __device__ __forceinline__ void run(const ModelDesc &m, const double *th, uint64_t pid, uint64_t iter,
+                                             double *rho, int coop = 0) {
+    NormalStream ns(m.seed, pid, PURPOSE_SIM, iter, coop);
+    dispatch(th, m.p, ns, rho);
+  }
+  // the forward run: the stream of `purpose` with the destination of sabc::emit on it; coop = 4 | 16: k_simulate_batch_team
+  static __device__ __forceinline__ void run_out(const ModelDesc &m, const double *th, uint64_t pid, uint32_t purpose,
+                                                 uint64_t iter, double *rho, double *out, long long stride, long long n_out,
+                                                 int coop = 0) {
+    NormalStream ns(m.seed, pid, purpose, iter, coop);
+    ns.set_outputs(out, stride, n_out);
+    dispatch(th, m.p, ns, rho);
+  }
+};
+}  // namespace sabc
+)SABC";
+
 // ---- the kernels of a unit: THE table ----
 // Name expression (what hipRTC instantiates) and slot of `k` per kernel.  Everything that walks the kernels -- the name
 // expressions, the lowered names of a cached module, the resolution of the slots, their number -- walks this, in this order;
 // cache files and code objects depend on it.  More than kNarrowStats statistics: the wide kernels in the slots of the narrow
-// ones and the launch chain only (persistent_fits is false there).
+// ones and the launch chain only (persistent_fits is false there).  A team-aware unit APPENDS k_update_team for 4 lanes x three
+// proposals, for 16 lanes x three proposals, then k_simulate_batch_team for 4 and for 16 lanes; every other unit's table is
+// what it was.
 struct KernelEntry {
   std::string name;
   hipFunction_t *slot;
@@ -284,7 +321,7 @@ struct KernelEntry {
 
 bool one_launch(int s, bool with_persistent) { return with_persistent && !source_wide(s); }
 
-std::vector<KernelEntry> kernel_table(int d, int s, bool with_persistent, RtcKernels *k) {
+std::vector<KernelEntry> kernel_table(int d, int s, bool with_persistent, RtcKernels *k, bool team_aware = false) {
   const std::string w = source_wide(s) ? "_wide" : "", ds = std::to_string(d) + ", " + std::to_string(s);
   const std::string mds = std::to_string((int)SABC_MODEL_USER) + ", " + ds;
   std::vector<KernelEntry> t;
@@ -299,6 +336,13 @@ std::vector<KernelEntry> kernel_table(int d, int s, bool with_persistent, RtcKer
       for (int p = 0; p < 3; ++p)
         t.push_back({"sabc::k_update_persistent<" + mds + ", " + std::to_string(p) + lanes + ">", &k->persistent[team][p]});
     }
+  if (team_aware && !source_wide(s)) {
+    for (int team = 1; team < 3; ++team)
+      for (int p = 0; p < 3; ++p)
+        t.push_back({"sabc::k_update_team<" + mds + ", " + std::to_string(p) + ", " + std::to_string(kPersistTeamLanes[team]) + ">", &k->update_team[team - 1][p]});
+    for (int team = 1; team < 3; ++team)
+      t.push_back({"sabc::k_simulate_batch_team<" + mds + ", " + std::to_string(kPersistTeamLanes[team]) + ">", &k->simulate_batch_team[team - 1]});
+  }
   return t;
 }
 
@@ -306,7 +350,8 @@ std::vector<KernelEntry> kernel_table(int d, int s, bool with_persistent, RtcKer
 bool load_kernels(const CachedModule &m, const RtcRequest &rq, RtcKernels *out, std::string *log) {
   RtcKernels k;
   if (hipModuleLoadData(&k.module, m.code.data()) != hipSuccess) { *log = "hipModuleLoadData of the simulator's code object failed"; return false; }
-  const std::vector<KernelEntry> table = kernel_table(rq.d, rq.s, rq.with_persistent, &k);
+  const std::vector<KernelEntry> table = kernel_table(rq.d, rq.s, rq.with_persistent, &k, rq.team_aware);
+  k.team_aware = rq.team_aware;
   for (size_t i = 0; i < table.size(); ++i)
     if (i >= m.lowered.size() || hipModuleGetFunction(table[i].slot, k.module, m.lowered[i].c_str()) != hipSuccess) {
       *log = "kernel not found in the simulator's module: " + table[i].name;
@@ -354,10 +399,10 @@ void rtc_release(RtcKernels *k) {
   if (k) *k = RtcKernels();
 }
 
-std::vector<std::string> rtc_kernel_names(int d, int s, bool with_persistent) {
+std::vector<std::string> rtc_kernel_names(int d, int s, bool with_persistent, bool team_aware) {
   RtcKernels unused;
   std::vector<std::string> names;
-  for (const KernelEntry &e : kernel_table(d, s, with_persistent, &unused)) names.push_back(e.name);
+  for (const KernelEntry &e : kernel_table(d, s, with_persistent, &unused, team_aware)) names.push_back(e.name);
   return names;
 }
 
@@ -371,17 +416,23 @@ int rtc_compile(const RtcRequest &rq, RtcKernels *out, std::string *log, size_t 
   HiprtcApi *api = hiprtc_api();
   if (!api) { *log = "libhiprtc.so could not be loaded: simulators from source need the hipRTC of ROCm"; return -1; }
   if (rq.d < 1 || rq.d > SABC_MAX_PARA || rq.s < 1 || rq.s > SABC_MAX_SOURCE_STATS) { *log = "n_para / n_stats out of range (a simulator from source: d <= 16, s <= 64)"; return -1; }
+  if (rq.team_aware && source_wide(rq.s)) {
+    *log = "a team-aware simulator (sabc_user_simulate_team<W>) has no wide form: n_stats <= 16 (the kernels for 16 < n_stats <= 64 run a lane per particle)";
+    return -1;
+  }
   const bool persistent = one_launch(rq.s, rq.with_persistent);
-  std::string src = std::string("#include \"update_kernel.hpp\"\n") + (persistent ? "#include \"persistent_kernel.hpp\"\n" : "") + kDataPreamble + "#line 1 \"f_dist.hip\"\n";
+  std::string src = std::string("#include \"update_kernel.hpp\"\n") + (persistent ? "#include \"persistent_kernel.hpp\"\n" : "") + kDataPreamble +
+                    (rq.team_aware ? kTeamDecl : "") + "#line 1 \"f_dist.hip\"\n";
   src += rq.source;
-  src += kUserSimTail;
+  src += rq.team_aware ? kTeamSimTail : kUserSimTail;
   RtcKernels unused;
-  const std::vector<KernelEntry> table = kernel_table(rq.d, rq.s, persistent, &unused);
+  const std::vector<KernelEntry> table = kernel_table(rq.d, rq.s, persistent, &unused, rq.team_aware);
   // extra compiler flags (e.g. -DSABC_NO_BITOP3: the two-instruction form of the Philox round's three-input XOR)
   const char *extra_env = std::getenv("SABC_RTC_EXTRA_FLAGS");
   const std::string extra = extra_env ? extra_env : "";
   std::string cache_key = std::to_string(rq.d) + "," + std::to_string(rq.s) + (rq.user_prior ? ",P" : "") + (persistent ? ",1L4L16" : "") + "," + extra;
   for (const char *g : kGeometry) cache_key += std::string(",") + g;
+  if (rq.team_aware) cache_key += std::string(",TEAM\n") + kTeamDecl + "\n" + kTeamSimTail;   // (a plain unit's key is what it was)
   cache_key += std::string("\n") + kDataPreamble + "\n" + kUserSimTail + "\n" + rq.source;
 
   if (out) {                                           // this process has compiled it: a failure here is an error

@@ -23,10 +23,22 @@ struct RtcKernels {
   hipFunction_t stats = nullptr;               // k_stats<D, S>
   hipFunction_t prior_op = nullptr;            // k_prior_op_t<D>
   hipFunction_t persistent[3][3] = {};         // [team][PROP]: k_update_persistent<USER, D, S, PROP, kPersistTeamLanes[team]> (persistent_kernel.hpp)
+  // a team-aware unit only (RtcRequest::team_aware), [team - 1] = a quad | a row of 16 lanes per particle:
+  hipFunction_t update_team[2][3] = {};        // [team - 1][PROP]: k_update_team<USER, D, S, PROP, kPersistTeamLanes[team]>
+  hipFunction_t simulate_batch_team[2] = {};   // [team - 1]: k_simulate_batch_team<USER, D, S, kPersistTeamLanes[team]>
+  bool team_aware = false;                     // the unit was compiled from a source that defines sabc_user_simulate_team<W>
+  int chain_lanes = 1;                         // ... and its handle runs it with this many lanes per particle on the launch chain and in the
+                                               // forward run (1 | 4 | 16; set by the backend at registration, not by rtc_compile)
 };
 
 // `source` must define
 //     __device__ void sabc_user_simulate(const double *theta, const double *params, sabc::NormalStream &rng, double *rho_out);
+// or, team_aware (the storage of sabc::Sample<N, W> depends on the lanes W = 1 | 4 | 16 that run a particle side by side, so the
+// simulator gets W as a template argument instead of reading rng.coop),
+//     template <int W> __device__ void sabc_user_simulate_team(const double *theta, const double *params, sabc::NormalStream &rng, double *rho_out);
+// All lanes of a team see the same data and must make the same requests of rng and of a Sample, in the same order.  Such a unit
+// also holds k_update_team and k_simulate_batch_team for 4 and 16 lanes (one compilation serves every choice of width); it has
+// no wide form: s <= kNarrowStats.
 // `csrc_dir` holds update_kernel.hpp and what it includes.
 // user_prior: the source also defines sabc_user_prior_sample / sabc_user_prior_logpdf (sabc_config::prior_joint = 3).
 // with_persistent: also compile k_update_persistent<USER, D, S, PROP, LANES> (small shards: the updates of a call in one launch;
@@ -36,6 +48,7 @@ struct RtcRequest {
   int d = 0, s = 0;
   std::string csrc_dir;
   bool user_prior = false, with_persistent = false;
+  bool team_aware = false;
 };
 
 // Compiles the request for gfx950 and loads its kernels into `out`.  Returns 0 or -1 with the compiler log / error text in `log`.
@@ -45,7 +58,9 @@ int rtc_compile(const RtcRequest &request, RtcKernels *out, std::string *log, si
 void rtc_release(RtcKernels *k);
 // read-only views of what rtc_compile works from (tests/rtc_host): the name expressions of the unit's kernels in table order,
 // and the files whose names and text the disk cache's key covers (hash, optional: what the key takes of them)
-std::vector<std::string> rtc_kernel_names(int d, int s, bool with_persistent);
+// team_aware: behind them, in this order, k_update_team for 4 lanes x three proposals, for 16 lanes x three proposals,
+// k_simulate_batch_team for 4 and for 16 lanes
+std::vector<std::string> rtc_kernel_names(int d, int s, bool with_persistent, bool team_aware = false);
 std::vector<std::string> rtc_unit_headers(const std::string &csrc_dir, uint64_t *hash = nullptr);
 // Observed data (sabc_set_device_data): every source-compiled unit defines one module-scope __constant__ variable of this
 // layout ahead of the user's text (rtc.cpp: kDataPreamble, which declares the same struct to the device compiler); the

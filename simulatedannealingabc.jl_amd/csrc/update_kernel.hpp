@@ -314,6 +314,45 @@ k_update(const ModelDesc m, const StepArgs c, const ControlBlock *__restrict__ c
   block_reduce_store<NP, kUpdateBlock>(acc, partials + (int64_t)blockIdx.x * NP);
 }
 
+// K4 on the launch chain with a TEAM of LANES = 4 | 16 lanes per particle (a team-aware simulator from source, rtc.hpp: its
+// sabc::Sample is spread over the team): k_update with update_particle<.., LANES> -- the body k_update_persistent runs for a
+// team.  Same arguments, same streams, same partial rows as k_update, and as many of them: a workgroup takes its
+// update_block_threads(S) particles in LANES trips of a team each, so the coarse ECDF index it loads into LDS (8 or 16 KB per
+// statistic) serves as many particles as in k_update and the control step reads as many rows.  A row is the sum over the
+// trips of what block_reduce_store<.., LANES> sums of a trip's teams (their first lanes hold the terms, the others zeros).
+// t < act_n and the prior's gate are uniform over a team: DPP reads from lanes of the own team only.
+// Two waves per SIMD is all the launch bounds ask for -- one workgroup of 512 per CU --: a sample of 32 slots per lane is 64
+// registers and a cross-lane step holds as many again for the partners' values, which k_update's cap of 80 would send to scratch.
+constexpr int kTeamMinWaves = 2;
+template <int MODEL, int D, int S, int PROP, int LANES>
+__global__ void __launch_bounds__(update_block_threads(S), kTeamMinWaves)
+k_update_team(const ModelDesc m, const StepArgs c, const ControlBlock *__restrict__ cb, const PopPtrs pp, const CdfPtrs cdf,
+              const PartnerView pv, const int64_t act_lo, const int64_t act_n, double *__restrict__ partials) {
+  static_assert(LANES == 4 || LANES == 16, "a quad or a row of 16 lanes per particle");
+  constexpr int NP = n_partials(D, S);
+  if (cb->halt) return;                    // queued ahead of a resample decision that fired (uniform)
+  rng_tables_load();
+  constexpr int kUpdateBlock = update_block_threads(S), kCoarse = cdf_coarse_entries(S), kPerTrip = kUpdateBlock / LANES;
+  __shared__ double cidx[S][kCoarse];
+  load_coarse_index<S>(cdf, cidx);
+  __syncthreads();                         // publishes both the generator tables and the index
+  double acc[NP];
+#pragma unroll
+  for (int q = 0; q < NP; ++q) acc[q] = 0.0;
+#pragma nounroll
+  for (int trip = 0; trip < LANES; ++trip) {
+    const int64_t t = (int64_t)blockIdx.x * kUpdateBlock + trip * kPerTrip + (int)(threadIdx.x / LANES);
+    if (t < act_n) {
+      const int64_t li = act_lo + t;
+      double term[NP];
+      update_particle<MODEL, D, S, PROP, false, LANES>(m, c.iter, c.prop_p0, c.prop_p1, cb, pp, cdf, pv, cidx, li, (uint64_t)(pp.gid0 + li), term);
+#pragma unroll
+      for (int q = 0; q < NP; ++q) acc[q] += term[q];
+    }
+  }
+  block_reduce_store<NP, kUpdateBlock, LANES>(acc, partials + (int64_t)blockIdx.x * NP);
+}
+
 // moment sums of the shard as it stands (after a resample, or at update_population! entry :284)
 template <int D, int S>
 __global__ void __launch_bounds__(kBlock)
@@ -374,10 +413,16 @@ k_prior_op_t(const ModelDesc m, const uint64_t pid0, const int64_t n, double *__
 // output buffer, or on another purpose than PURPOSE_SIM, runs through the second entry of its Sim (run_out: the stream carries
 // the destination of sabc::emit, outputs [n_out][n]); every other launch -- out = nullptr, PURPOSE_SIM: sabc_op_simulate, the
 // host-prior path -- and every built-in model takes run as before.
-template <int MODEL, int D, int S>
+// LANES = 4 | 16 (k_simulate_batch_team, a team-aware unit only): the lanes of a team run this row together.
+template <int MODEL, int D, int S, int LANES = 1>
 __device__ __forceinline__ void simulate_row(const ModelDesc &m, const double *th, const uint64_t pid, const uint64_t iter,
                                              double *rho, double *out, const int64_t out_stride, const int64_t n_out,
                                              const uint32_t purpose) {
+  if constexpr (LANES > 1) {
+    if (out || purpose != PURPOSE_SIM) Sim<MODEL, D, S>::run_out(m, th, pid, purpose, iter, rho, out, out_stride, n_out, LANES);
+    else Sim<MODEL, D, S>::run(m, th, pid, iter, rho, LANES);
+    return;
+  }
   if constexpr (MODEL == SABC_MODEL_USER) {
     if (out || purpose != PURPOSE_SIM) {
       Sim<MODEL, D, S>::run_out(m, th, pid, purpose, iter, rho, out, out_stride, n_out);
@@ -407,6 +452,32 @@ k_simulate_batch(const ModelDesc m, const double *__restrict__ theta, const int6
   }
 #pragma unroll
   for (int j = 0; j < S; ++j) rho_out[(int64_t)j * n + i] = rho[j];
+}
+
+// k_simulate_batch with a team of LANES = 4 | 16 lanes per row (a team-aware simulator from source): row i is the global thread
+// id divided by LANES, so i < n and the gate are uniform over a team; the team's first lane writes the distances (every lane
+// holds them), and sabc::emit / Sample::emit write each output once.  Gate, output buffer and purposes as in k_simulate_batch.
+template <int MODEL, int D, int S, int LANES>
+__global__ void __launch_bounds__(kBlock)
+k_simulate_batch_team(const ModelDesc m, const double *__restrict__ theta, const int64_t n, const uint64_t pid0,
+                      const uint64_t iter, double *__restrict__ rho_out, const unsigned char *__restrict__ gate,
+                      double *__restrict__ out, const int64_t n_out, const uint32_t purpose) {
+  static_assert(LANES == 4 || LANES == 16, "a quad or a row of 16 lanes per row");
+  rng_tables_init();
+  const int64_t i = ((int64_t)blockIdx.x * kBlock + threadIdx.x) / LANES;
+  if (i >= n) return;
+  double th[D], rho[S];
+#pragma unroll
+  for (int j = 0; j < S; ++j) rho[j] = 0.0;
+  if (!gate || gate[i]) {
+#pragma unroll
+    for (int k = 0; k < D; ++k) th[k] = theta[(int64_t)k * n + i];
+    simulate_row<MODEL, D, S, LANES>(m, th, pid0 + (uint64_t)i, iter, rho, out ? out + i : nullptr, n, n_out, purpose);
+  }
+  if ((threadIdx.x & (LANES - 1)) == 0) {
+#pragma unroll
+    for (int j = 0; j < S; ++j) rho_out[(int64_t)j * n + i] = rho[j];
+  }
 }
 
 // ------------------------------------------------------------------------------------------

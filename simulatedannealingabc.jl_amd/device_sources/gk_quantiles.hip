@@ -15,6 +15,27 @@
 #if !defined(GKQ_N_DRAWS) || !defined(GKQ_N_STATS)
 #error "gk_quantiles.hip: GKQ_N_DRAWS and GKQ_N_STATS are defined by the model class in front of this text"
 #endif
+#if defined(GKQ_TEAM)
+// The team-aware form (GandKQuantiles(..., team_lanes=)): the same draws, statistics and outputs through sabc::Sample<N, W>
+// (csrc/team_sample.hpp) -- each of the W lanes that run the particle generates its own blocks of the stream, applies the
+// quantile function to its own normals only and keeps the results; the team sorts them in registers, and every lane reads the
+// same quantiles.  W = 1, or more than 32 values per lane: the sample every lane holds whole, as below.
+template <int W>
+__device__ void sabc_user_simulate_team(const double *theta, const double *p, sabc::NormalStream &rng, double *rho) {
+  constexpr int N = GKQ_N_DRAWS;
+  const double A = theta[0], B = theta[1], g = theta[2], k = theta[3], c = p[1];
+  const auto draw = [&](const double z) {
+    const double w = sabc::exp_tab_upto<710>(-0.5 * k * sabc::neg2_log_tab(fma(z, z, 1.0)));     // (1 + z^2)^k
+    return A + B * (1.0 + c * sabc::tanh_abs_tab(g * z / 2.0)) * w * z;
+  };
+  sabc::Sample<N, W> x;
+  x.fill_normals(rng, draw);
+  x.sort();
+#pragma unroll
+  for (int j = 0; j < GKQ_N_STATS; ++j) rho[j] = sabc::finite_or_big(fabs(x.quantile(sabc::data_at(j, 0)) - sabc::data_at(j, 1)));
+  x.emit(rng, 0);
+}
+#else
 __device__ void sabc_user_simulate(const double *theta, const double *p, sabc::NormalStream &rng, double *rho) {
   constexpr int N = GKQ_N_DRAWS;
   const double A = theta[0], B = theta[1], g = theta[2], k = theta[3], c = p[1];
@@ -40,3 +61,4 @@ __device__ void sabc_user_simulate(const double *theta, const double *p, sabc::N
   if (sabc::emitting(rng))
     for (int i = 0; i < N; ++i) sabc::emit(rng, i, x[i]);
 }
+#endif

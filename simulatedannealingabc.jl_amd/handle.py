@@ -61,7 +61,11 @@ class SabcHandle:
         self._outputs_for = getattr(model, "n_outputs_for", None)      # ... and how many outputs it emits for given data
         self._data_segments = None                                     # the segments set_data was last given
         if getattr(model, "model_id", None) == _lib.MODEL_USER:
-            rc = self._L.sabc_register_device_simulator(self._h, model.source.encode())
+            team_lanes = getattr(model, "team_lanes", None)  # a team-aware source: sabc_user_simulate_team<W>
+            if team_lanes is None:
+                rc = self._L.sabc_register_device_simulator(self._h, model.source.encode())
+            else:
+                rc = self._L.sabc_register_device_simulator_team(self._h, model.source.encode(), int(team_lanes))
             if rc:
                 msg = self._L.sabc_last_error(self._h).decode("utf-8", "replace")
                 self.close()
@@ -410,6 +414,12 @@ class SabcHandle:
         """Lanes per particle of the last one-launch update: 16 | 4 = a row | a quad of lanes runs a particle and shares its
         generator blocks (<= 2048 | 16 384 particles per launch), 1 = a lane per particle, 0 = none yet."""
         return int(self._L.sabc_persistent_lanes(self._h))
+
+    @property
+    def chain_team_lanes(self):
+        """Lanes per particle of a team-aware source (`DeviceSource(..., team_lanes=)`) on the launch chain and in the forward
+        run: 1, 4 or 16; 0 for a source registered the ordinary way."""
+        return int(self._L.sabc_chain_team_lanes(self._h))
 
     @property
     def persistent_fallbacks(self):

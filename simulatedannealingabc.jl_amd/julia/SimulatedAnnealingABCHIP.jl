@@ -145,7 +145,12 @@ model_id(::HostDistance) = Int32(0)
 #      sabc::data_len(segment) / sabc::data_at(i, segment); an array of several dimensions is flattened in Julia's own
 #      (column-major) order.  With `data_names = (:y_obs, :t_obs)`, `sabc` and `update_population!` take that many extra
 #      positional arguments or keywords of those names, as the reference forwards args... / kwargs... to f_dist (:164,175,315):
-#      they become the segments in that order; in `update_population!` data that are not given leave the handle's ----
+#      they become the segments in that order; in `update_population!` data that are not given leave the handle's.
+#      `team_lanes` = 1, 4 or 16 (default `nothing`): the source is TEAM-AWARE -- it defines, instead of sabc_user_simulate,
+#          template <int W> __device__ void sabc_user_simulate_team(const double *theta, const double *params, sabc::NormalStream &rng, double *rho_out);
+#      with W the lanes that run one particle side by side, holds its sample in a sabc::Sample<N, W> (csrc/team_sample.hpp:
+#      fill_normals, fill, drawn, sort, at, order_statistic, quantile, emit) and runs with that many lanes per particle on the
+#      launch chain and in the forward run (sabc_register_device_simulator_team); n_stats <= 16 ----
 struct DeviceSource <: DeviceDistance
     source::String
     n_para::Int
@@ -154,23 +159,26 @@ struct DeviceSource <: DeviceDistance
     data::Vector{Vector{Float64}}
     data_names::Tuple
     validate::Function                   # segments -> nothing, or throws: what this model's source requires of its data
+    team_lanes::Int                      # 0: sabc_user_simulate | 1, 4, 16: sabc_user_simulate_team<W>, that many lanes per particle
 end
 no_data_check(segs) = nothing
 data_segment(x) = vec(collect(Float64, x))
 data_segments(x) = x === nothing ? Vector{Float64}[] :
                    (x isa Tuple || (x isa Vector && !(eltype(x) <: Real))) ? Vector{Float64}[data_segment(y) for y in x] :
                    Vector{Float64}[data_segment(x)]
-function DeviceSource(source, n_para, n_stats; params=Float64[], data=nothing, data_names=(), validate=no_data_check)
+function DeviceSource(source, n_para, n_stats; params=Float64[], data=nothing, data_names=(), validate=no_data_check, team_lanes=nothing)
+    team_lanes === nothing || team_lanes in (1, 4, 16) || throw(ArgumentError("team_lanes is nothing, 1, 4 or 16"))
+    team_lanes === nothing || n_stats <= 16 || throw(ArgumentError("a team-aware source has at most 16 statistics"))
     segs = data_segments(data)
     isempty(segs) || validate(segs)
     length(segs) <= 8 || throw(ArgumentError("at most 8 data segments"))
     names = Tuple(Symbol(n) for n in data_names)
     (isempty(names) || isempty(segs) || length(names) == length(segs)) || throw(ArgumentError("one name in data_names per data segment"))
-    DeviceSource(source, n_para, n_stats, collect(Float64, params), segs, names, validate)
+    DeviceSource(source, n_para, n_stats, collect(Float64, params), segs, names, validate, team_lanes === nothing ? 0 : Int(team_lanes))
 end
 # the four positional arguments the struct took before it carried data (StochasticSIR, and callers' own code)
 DeviceSource(source, n_para, n_stats, params) = DeviceSource(source, n_para, n_stats; params=params)
-with_data(m::DeviceSource, segs) = DeviceSource(m.source, m.n_para, m.n_stats, m.params, segs, m.data_names, m.validate)
+with_data(m::DeviceSource, segs) = DeviceSource(m.source, m.n_para, m.n_stats, m.params, segs, m.data_names, m.validate, m.team_lanes)
 
 # the extra arguments of sabc / update_population! as data segments in the order of data_names; nothing if there are none
 function bind_data(f_dist::DeviceDistance, kwargs)
@@ -274,23 +282,25 @@ check_series_data(segs) = (length(segs) == 2 && length(segs[1]) == length(segs[2
     throw(ArgumentError("t_obs is increasing, holds at least one value and is as long as I_obs"))
 
 """
-    GandKQuantiles(probs, q_obs; n_draws=128, c=0.8)
-    GandKQuantiles(y_obs; probs=(1:7) ./ 8, n_draws=length(y_obs), c=0.8)
+    GandKQuantiles(probs, q_obs; n_draws=128, c=0.8, team_lanes=nothing)
+    GandKQuantiles(y_obs; probs=(1:7) ./ 8, n_draws=length(y_obs), c=0.8, team_lanes=nothing)
 
 g-and-k, θ = (A, B, g, k), with any number of draws and any set of quantiles: ρ_j = |quantile(x_sim, probs[j]) − q_obs[j]| with
 Julia's default `quantile`.  Two data segments, `probs` and `q_obs` (1 to 16 values each); the second method takes `q_obs`
 from a sample.  A `DeviceSource` of device_sources/gk_quantiles.hip, which sorts the draws with `sabc::sort_ascending`.
+`team_lanes` = 1, 4 or 16: its team-aware form -- the sample in a `sabc::Sample`, drawn and sorted by that many lanes together.
 """
-function GandKQuantiles(probs, q_obs; n_draws::Integer=128, c=0.8)
+function GandKQuantiles(probs, q_obs; n_draws::Integer=128, c=0.8, team_lanes=nothing)
     2 <= n_draws <= 1024 || throw(ArgumentError("n_draws must be in 2..1024"))
     1 <= length(probs) <= 16 || throw(ArgumentError("1 to 16 quantiles"))
     text = read(joinpath(@__DIR__, "..", "device_sources", "gk_quantiles.hip"), String)
     n_q = length(probs)
-    DeviceSource("#define GKQ_N_DRAWS $(n_draws)\n#define GKQ_N_STATS $(n_q)\n" * text, 4, n_q; params=Float64[n_draws, c],
-                 data=(probs, q_obs), data_names=(:probs, :q_obs), validate=segs -> check_quantile_data(segs, n_q))
+    team = team_lanes === nothing ? "" : "#define GKQ_TEAM 1\n"
+    DeviceSource("#define GKQ_N_DRAWS $(n_draws)\n#define GKQ_N_STATS $(n_q)\n" * team * text, 4, n_q; params=Float64[n_draws, c],
+                 data=(probs, q_obs), data_names=(:probs, :q_obs), validate=segs -> check_quantile_data(segs, n_q), team_lanes=team_lanes)
 end
-GandKQuantiles(y_obs; probs=(1:7) ./ 8, n_draws::Integer=length(y_obs), c=0.8) =
-    GandKQuantiles(probs, type7_quantiles(sort(data_segment(y_obs)), probs); n_draws=n_draws, c=c)
+GandKQuantiles(y_obs; probs=(1:7) ./ 8, n_draws::Integer=length(y_obs), c=0.8, team_lanes=nothing) =
+    GandKQuantiles(probs, type7_quantiles(sort(data_segment(y_obs)), probs); n_draws=n_draws, c=c, team_lanes=team_lanes)
 # Julia's default quantile (Statistics.quantile, type 7) of an ascending vector, without the dependency
 function type7_quantiles(x, probs)
     map(probs) do p
@@ -491,7 +501,12 @@ function create_handle(f_dist::DeviceDistance, prior; n_particles, algorithm, v,
         end
     end
     if f_dist isa DeviceSource
-        check(h[], ccall((:sabc_register_device_simulator, libsabc), Cint, (Ptr{Cvoid}, Cstring), h[], f_dist.source))
+        if f_dist.team_lanes == 0
+            check(h[], ccall((:sabc_register_device_simulator, libsabc), Cint, (Ptr{Cvoid}, Cstring), h[], f_dist.source))
+        else
+            check(h[], ccall((:sabc_register_device_simulator_team, libsabc), Cint, (Ptr{Cvoid}, Cstring, Int32), h[], f_dist.source,
+                             Int32(f_dist.team_lanes)))
+        end
         isempty(f_dist.data) || set_device_data!(h[], f_dist.data)
     end
     if f_dist isa HostDistance

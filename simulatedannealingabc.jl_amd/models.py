@@ -204,12 +204,34 @@ class DeviceSource(DeviceDistance):
     max, never a branch --: which elements meet depends on n alone, so the lanes of a wave index their arrays alike, and a
     lane, a quad or a row of lanes per particle return the same bits (a sorted array is unique).  A NaN enters as +inf, the
     built-in g-and-k model's policy, and comes out last; -0.0 and +0.0 compare equal.  A sort written by hand in the source is a
-    data-dependent loop that diverges across the wave.  In the one-launch form every lane of a team sorts the whole sample (there
-    is no cooperative form yet).  `GandKQuantiles` is the shipped model on it."""
+    data-dependent loop that diverges across the wave.  `GandKQuantiles` is the shipped model on it.
+
+    The cooperative form, `team_lanes` = 1, 4 or 16 (None: everything above, the entry point `sabc_user_simulate`): the source
+    defines instead
+        template <int W> __device__ void sabc_user_simulate_team(const double *theta, const double *params,
+                                                                 sabc::NormalStream &rng, double *rho_out);
+    with W = 1, 4 or 16 the lanes that run this particle side by side, and runs with `team_lanes` lanes per particle on the launch
+    chain and in the forward run (`simulate_outputs`, `posterior_predictive`); the one-launch form of small populations keeps
+    choosing its own team.  All lanes of a team see the same data and must make the same requests, in the same order.
+    `sabc::Sample<N, W> x` (csrc/team_sample.hpp) holds N doubles of the particle spread over the team, in registers:
+    `x.fill_normals(rng, f)` (element i = f(z_i), the next N normals in stream order -- ceil(N / 2) whole blocks, each lane
+    generating and transforming its own), `x.fill(g)` (element i = g(i)), `x.drawn(i)` before and `x.at(i)`,
+    `x.order_statistic(rank)`, `x.quantile(p)` after `x.sort()` -- a bitonic network, min and max between registers of a lane,
+    DPP between lanes, no LDS --, and `x.emit(rng, first_output)` (the current order, each value written once).  A NaN enters as
+    +inf.  More than 32 slots per lane (N > 32 W), or W = 1: every lane holds the whole sample as before, so any N compiles.
+    n_stats <= 16."""
     model_id = _lib.MODEL_USER
 
     def __init__(self, hip_source: str, n_para: int, n_stats: int, params=(), data=None, data_names=None, n_outputs=None,
-                 output_names=None):
+                 output_names=None, team_lanes=None):
+        if team_lanes is not None:
+            if isinstance(team_lanes, bool) or team_lanes not in (1, 4, 16):
+                raise ValueError(f"team_lanes is None (sabc_user_simulate) or 1, 4 or 16 lanes per particle (sabc_user_simulate_team<W>), got {team_lanes!r}")
+            if int(n_stats) > _lib.NARROW_STATS:
+                raise ValueError(f"a team-aware source has at most {_lib.NARROW_STATS} statistics (the kernels for more run a lane per "
+                                 f"particle), got n_stats = {n_stats}")
+            team_lanes = int(team_lanes)
+        self.team_lanes = team_lanes
         self.output_names = None if output_names is None else tuple(str(x) for x in output_names)
         if n_outputs is None and self.output_names is not None:
             n_outputs = len(self.output_names)
@@ -291,7 +313,11 @@ class DeviceSource(DeviceDistance):
         with_prior: the source also defines the prior (SourcePrior)."""
         import ctypes as C
         log = C.create_string_buffer(1 << 16)
-        fn = _lib.lib().sabc_op_compile_device_simulator_with_prior if with_prior else _lib.lib().sabc_op_compile_device_simulator
+        L = _lib.lib()
+        if self.team_lanes is not None:
+            fn = L.sabc_op_compile_device_simulator_team_with_prior if with_prior else L.sabc_op_compile_device_simulator_team
+        else:
+            fn = L.sabc_op_compile_device_simulator_with_prior if with_prior else L.sabc_op_compile_device_simulator
         rc = fn(self.source.encode(), self.n_para[0], self.n_stats, log, len(log))
         if rc:
             raise _lib.SABCError(rc, "compiling the device simulator failed:\n" + log.value.decode("utf-8", "replace"))
@@ -441,27 +467,34 @@ class GandKQuantiles(DeviceSource):
     `n_draws` and `c` are params.  `from_observations(y_obs)` takes `q_obs` from a sample with `np.quantile`.
     Source: device_sources/gk_quantiles.hip, which sorts the draws with `sabc::sort_ascending` -- n_draws is a compile-time constant
     of the source, up to 32 draws the sorting network runs on registers.  Outputs: the sorted sample (`posterior_predictive`
-    gives [n, n_rep, n_draws], ascending along the last axis)."""
+    gives [n, n_rep, n_draws], ascending along the last axis).
+    `team_lanes` = 1, 4 or 16 (None: the above): the same model through `sabc::Sample<n_draws, W>` -- the sample spread over a team
+    of lanes that draws, transforms and sorts it together, `team_lanes` lanes per particle on the launch chain and in the forward
+    run (`DeviceSource`, the cooperative form).  The same statistics and outputs; the results are the default form's up to the
+    order of the partial sums."""
     MAX_QUANTILES = 16
     MAX_DRAWS = 1024                 # the sample is 8 n_draws bytes of private memory per lane
     OCTILES = tuple(j / 8 for j in range(1, 8))
 
-    def __init__(self, probs, q_obs, n_draws=128, c=0.8, data_names=("probs", "q_obs")):
+    def __init__(self, probs, q_obs, n_draws=128, c=0.8, data_names=("probs", "q_obs"), team_lanes=None):
         if isinstance(n_draws, bool) or int(n_draws) != n_draws or not 2 <= int(n_draws) <= self.MAX_DRAWS:
             raise ValueError(f"n_draws must be an integer in 2..{self.MAX_DRAWS}, got {n_draws!r}")
         probs, q_obs = _segment(probs), _segment(q_obs)
         if not 1 <= len(probs) <= self.MAX_QUANTILES:
             raise ValueError(f"1 to {self.MAX_QUANTILES} quantiles, got {len(probs)}")
         self.n_draws, self.c = int(n_draws), float(c)
-        super().__init__(f"#define GKQ_N_DRAWS {self.n_draws}\n#define GKQ_N_STATS {len(probs)}\n" + device_source_text("gk_quantiles"),
-                         4, len(probs), [self.n_draws, self.c], data=[probs, q_obs], data_names=data_names, n_outputs=self.n_draws)
+        team = "" if team_lanes is None else "#define GKQ_TEAM 1\n"
+        super().__init__(f"#define GKQ_N_DRAWS {self.n_draws}\n#define GKQ_N_STATS {len(probs)}\n" + team + device_source_text("gk_quantiles"),
+                         4, len(probs), [self.n_draws, self.c], data=[probs, q_obs], data_names=data_names, n_outputs=self.n_draws,
+                         team_lanes=team_lanes)
 
     @classmethod
-    def from_observations(cls, y_obs, probs=OCTILES, n_draws=None, c=0.8):
+    def from_observations(cls, y_obs, probs=OCTILES, n_draws=None, c=0.8, team_lanes=None):
         """The model for a sample `y_obs`: q_obs = np.quantile(y_obs, probs) and, unless given, as many draws per simulation as
         there are observations."""
         y_obs = _segment(y_obs)
-        return cls(probs, np.quantile(y_obs, _segment(probs)), n_draws=len(y_obs) if n_draws is None else n_draws, c=c)
+        return cls(probs, np.quantile(y_obs, _segment(probs)), n_draws=len(y_obs) if n_draws is None else n_draws, c=c,
+                   team_lanes=team_lanes)
 
     def validate_data(self, segments):
         # the source reads probs[j] and q_obs[j] and writes rho[j] for every j < n_stats
