@@ -187,3 +187,5 @@ SABC_SORT_HD double quantile(const double *sorted, int n, double p) {
 }
 
 }  // namespace sabc
+
+#include "sample_reduce.hpp"   // sabc::tree_sum, count_less, count_less_equal: what a sorted sample is summed and compared with

@@ -37,7 +37,15 @@
 // All lanes of a team hold the same particle and make the same calls in the same order -- the rule NormalStream states --, and a
 // read-out returns the same value on every lane of the team.  A rank known only at run time (uniform over the team) selects
 // over the slots and picks the lane by DPP: the slots stay registers.
+//
+// Reductions (sample_reduce.hpp has the definition): sum(g), max(g), min(g) over g(i, value) with i the element's index in the
+// current order.  A lane adds the tree of its own M slots (r and r ^ 1, then ^ 2, ..), the team follows with a butterfly over
+// the lane distances 1, 2, 4, 8 -- xor_lane and one v_add_f64 per step, a + b == b + a to the bit, so every lane ends with the
+// same value; no LDS, no barrier, no atomic.  A slot whose element index is >= N adds +0.0 and takes no part in a maximum.
+// After sort() position q M + r holds rank q M + r: in-lane levels are the low bits, the lanes the high bits of the canonical
+// tree over the rank, whatever W is -- the same bits for 1, 4 and 16 lanes and for the replicated store.
 #pragma once
+#include "sample_reduce.hpp"
 #include "sort_network.hpp"
 
 namespace sabc {
@@ -244,6 +252,48 @@ struct SampleStore {
   __device__ __forceinline__ double quantile(const double p) const {
     return quantile_at<N>([&](const int i) { return at(i); }, p);
   }
+  static __device__ __forceinline__ double team_add(double s) {
+    s = s + xor_lane<1>(s);
+    s = s + xor_lane<2>(s);
+    if constexpr (W == 16) {
+      s = s + xor_lane<4>(s);
+      s = s + xor_lane<8>(s);
+    }
+    return s;
+  }
+  template <bool MAX>
+  static __device__ __forceinline__ double team_extreme(double s) {
+    const auto pick = [](const double a, const double b) { return MAX ? sortnet::max_(a, b) : sortnet::min_(a, b); };
+    s = pick(s, xor_lane<1>(s));
+    s = pick(s, xor_lane<2>(s));
+    if constexpr (W == 16) {
+      s = pick(s, xor_lane<4>(s));
+      s = pick(s, xor_lane<8>(s));
+    }
+    return s;
+  }
+  template <class G>
+  __device__ __forceinline__ double sum(G &&g) const {
+    const int q = lane();
+    double t[M];
+#pragma unroll
+    for (int r = 0; r < M; ++r) {
+      const int i = element(q, r);
+      t[r] = i < N ? g(i, v[r]) : 0.0;
+    }
+    return reduce::finish_sum(team_add(reduce::lane_tree(t)));
+  }
+  template <bool MAX, class G>
+  __device__ __forceinline__ double extreme(G &&g) const {
+    const int q = lane();
+    double s = MAX ? -sortnet::inf_(0.0) : sortnet::inf_(0.0);
+#pragma unroll
+    for (int r = 0; r < M; ++r) {
+      const int i = element(q, r);
+      if (i < N) s = MAX ? sortnet::max_(s, g(i, v[r])) : sortnet::min_(s, g(i, v[r]));
+    }
+    return team_extreme<MAX>(s);
+  }
   __device__ __forceinline__ void emit(NormalStream &rng, const long long first_output) const {
     if (!emitting(rng)) return;
     const int q = lane();
@@ -284,6 +334,16 @@ struct SampleStore<N, W, false> {
   __device__ __forceinline__ double at(const int i) const { return x[i]; }
   __device__ __forceinline__ double order_statistic(const int rank) const { return sabc::order_statistic(x, N, rank); }
   __device__ __forceinline__ double quantile(const double p) const { return sabc::quantile(x, N, p); }
+  template <class G>
+  __device__ __forceinline__ double sum(G &&g) const {
+    return reduce::tree_sum_of(N, [&](const int i) { return g(i, x[i]); });
+  }
+  template <bool MAX, class G>
+  __device__ __forceinline__ double extreme(G &&g) const {
+    double s = MAX ? -sortnet::inf_(0.0) : sortnet::inf_(0.0);
+    for (int i = 0; i < N; ++i) s = MAX ? sortnet::max_(s, g(i, x[i])) : sortnet::min_(s, g(i, x[i]));
+    return s;
+  }
   __device__ __forceinline__ void emit(NormalStream &rng, const long long first_output) const {
     if (!emitting(rng) || (threadIdx.x & (unsigned)(W - 1)) != 0) return;
     for (int i = 0; i < N; ++i) sabc::emit(rng, first_output + i, x[i]);
@@ -298,11 +358,43 @@ struct SampleStore<N, W, false> {
 // at(i) (rank i, 0-based), order_statistic(rank) (1-based, +inf outside [1, N]), quantile(p) (type 7) after it;
 // emit(rng, first_output): element r of the current order -- draw order before the sort, rank order after -- to output
 // first_output + r, each value written once.
+// Reductions, the same value on every lane of the team (sample_reduce.hpp: the canonical tree; i = the element's index in the
+// current order, draw index before the sort, 0-based rank after it): sum(g), max(g), min(g) over g(i, value); sum(), mean();
+// moments(mean, var): two passes, var = sum (x - mean)^2 / (N - 1), 0 for N = 1.  After sort() sum gives the same bits for every
+// W; max and min always do.  Distances to an ascending observed sample in data segment seg, after sort():
+// wasserstein1(seg) = sum_i |x_(i) - y_i| / N and wasserstein2_squared(seg) = sum_i (x_(i) - y_i)^2 / N (data_len(seg) == N: each
+// lane reads its own M consecutive observations), ks(seg) the Kolmogorov-Smirnov distance for any data_len(seg) >= 1
+// (N data_len(seg) < 2^53).
 template <int N, int W>
 struct Sample : teamsort::SampleStore<N, W, teamsort::spread(N, W)> {
   static_assert(N >= 1, "a sample holds at least one value");
   static constexpr int size = N, lanes = W;
   static constexpr bool spread = teamsort::spread(N, W);
+  using Store = teamsort::SampleStore<N, W, teamsort::spread(N, W)>;
+  using Store::sum;
+
+  template <class G> __device__ __forceinline__ double max(G &&g) const { return Store::template extreme<true>(g); }
+  template <class G> __device__ __forceinline__ double min(G &&g) const { return Store::template extreme<false>(g); }
+  __device__ __forceinline__ double sum() const { return Store::sum([](const int, const double x) { return x; }); }
+  __device__ __forceinline__ double mean() const { return sum() / (double)N; }
+  __device__ __forceinline__ void moments(double &mean_out, double &var_out) const {
+    const double m = mean();
+    mean_out = m;
+    var_out = N > 1 ? Store::sum([&](const int, const double x) { return (x - m) * (x - m); }) / (double)(N > 1 ? N - 1 : 1) : 0.0;
+  }
+  __device__ __forceinline__ double wasserstein1(const int seg = 0) const {
+    return Store::sum([&](const int i, const double x) { return __builtin_fabs(x - data_at(i, seg)); }) / (double)N;
+  }
+  __device__ __forceinline__ double wasserstein2_squared(const int seg = 0) const {
+    return Store::sum([&](const int i, const double x) { const double d = x - data_at(i, seg); return d * d; }) / (double)N;
+  }
+  __device__ __forceinline__ double ks(const int seg = 0) const {
+    const long long m = data_len(seg);
+    const double top = Store::template extreme<true>([&](const int i, const double x) {
+      return reduce::ks_term(i, N, m, count_less(x, seg), count_less_equal(x, seg));
+    });
+    return top / ((double)N * (double)m);
+  }
 };
 
 }  // namespace sabc

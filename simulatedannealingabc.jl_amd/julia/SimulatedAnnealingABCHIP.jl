@@ -20,7 +20,7 @@ import Dates
 import Base: show
 
 export sabc, update_population!, RandomWalk, DifferentialEvolution, StretchMove,
-       DeviceDistance, GaussianIID, Gaussian2D, GandK, LotkaVolterra, DeviceSource, StochasticSIR, LotkaVolterraF32, NormalMoments, StochasticSIRSeries, GandKQuantiles, SourcePrior,
+       DeviceDistance, GaussianIID, Gaussian2D, GandK, LotkaVolterra, DeviceSource, StochasticSIR, LotkaVolterraF32, NormalMoments, StochasticSIRSeries, GandKQuantiles, GandKSample, SourcePrior,
        comm_unique_id, simulate_outputs, posterior_predictive
 
 const libsabc = get(ENV, "SABC_HIP_LIB", joinpath(@__DIR__, "..", "libsabc_hip.so"))
@@ -149,7 +149,8 @@ model_id(::HostDistance) = Int32(0)
 #      `team_lanes` = 1, 4 or 16 (default `nothing`): the source is TEAM-AWARE -- it defines, instead of sabc_user_simulate,
 #          template <int W> __device__ void sabc_user_simulate_team(const double *theta, const double *params, sabc::NormalStream &rng, double *rho_out);
 #      with W the lanes that run one particle side by side, holds its sample in a sabc::Sample<N, W> (csrc/team_sample.hpp:
-#      fill_normals, fill, drawn, sort, at, order_statistic, quantile, emit) and runs with that many lanes per particle on the
+#      fill_normals, fill, drawn, sort, at, order_statistic, quantile, emit; sum, max, min, mean, moments and, against a sorted
+#      data segment, wasserstein1, wasserstein2_squared, ks -- csrc/sample_reduce.hpp) and runs with that many lanes per particle on the
 #      launch chain and in the forward run (sabc_register_device_simulator_team); n_stats <= 16 ----
 struct DeviceSource <: DeviceDistance
     source::String
@@ -312,6 +313,32 @@ end
 # the source reads probs[j] and q_obs[j] and writes ρ[j] for every j < n_stats
 check_quantile_data(segs, n_q) = (length(segs) == 2 && length(segs[1]) == length(segs[2]) == n_q && all(p -> 0 <= p <= 1, segs[1])) ||
     throw(ArgumentError("probs and q_obs hold $(n_q) values each, every probability in [0, 1]"))
+"""
+    GandKSample(y_obs; distance=(:wasserstein, :ks), n_draws=length(y_obs), c=0.8, team_lanes=nothing)
+
+g-and-k, θ = (A, B, g, k), compared with the observed sample as a whole: `distance` = `:wasserstein` (ρ = Σ_i |x_(i) − y_(i)| / n
+between the sorted samples; `n_draws == length(y_obs)`), `:ks` (Kolmogorov–Smirnov; any two lengths) or both, one statistic per
+name in the order given.  One data segment, `y_obs`, kept sorted (the constructor sorts it; data that arrive with a call must be
+ascending).  A `DeviceSource` of device_sources/gk_sample.hip on `sabc::tree_sum`, `sabc::count_less` and `sabc::count_less_equal`
+(csrc/sample_reduce.hpp); `team_lanes` = 1, 4 or 16: the same through `sabc::Sample` (`wasserstein1`, `ks`), the same bits.
+"""
+function GandKSample(y_obs; distance=(:wasserstein, :ks), n_draws::Integer=length(y_obs), c=0.8, team_lanes=nothing)
+    names = distance isa Union{Symbol,String} ? (Symbol(distance),) : Tuple(Symbol(d) for d in distance)
+    (!isempty(names) && allunique(names) && all(d -> d in (:wasserstein, :ks), names)) ||
+        throw(ArgumentError("distance is :wasserstein, :ks or both, each once"))
+    1 <= n_draws <= 1024 || throw(ArgumentError("n_draws must be in 1..1024"))
+    text = read(joinpath(@__DIR__, "..", "device_sources", "gk_sample.hip"), String)
+    head = "#define GKS_N_DRAWS $(n_draws)\n" * join("#define GKS_$(uppercase(String(d))) $(j - 1)\n" for (j, d) in enumerate(names))
+    team = team_lanes === nothing ? "" : "#define GKS_TEAM 1\n"
+    rank_with_rank = :wasserstein in names
+    DeviceSource(head * team * text, 4, length(names); params=Float64[n_draws, c], data=(sort(data_segment(y_obs)),), data_names=(:y_obs,),
+                 validate=segs -> check_sample_data(segs, Int(n_draws), rank_with_rank), team_lanes=team_lanes)
+end
+# the source reads y[i] for every i < n_draws (:wasserstein) and searches an ascending y (:ks); the counts are exact below 2^53
+check_sample_data(segs, n_draws, rank_with_rank) =
+    (length(segs) == 1 && length(segs[1]) >= 1 && all(isfinite, segs[1]) && issorted(segs[1]) &&
+     (!rank_with_rank || length(segs[1]) == n_draws) && n_draws * length(segs[1]) < 2^53) ||
+    throw(ArgumentError("y_obs is one ascending segment of finite values" * (rank_with_rank ? ", $(n_draws) of them (distance :wasserstein)" : "")))
 """
     SourcePrior(d)
 

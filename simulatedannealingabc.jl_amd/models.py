@@ -219,7 +219,19 @@ class DeviceSource(DeviceDistance):
     `x.order_statistic(rank)`, `x.quantile(p)` after `x.sort()` -- a bitonic network, min and max between registers of a lane,
     DPP between lanes, no LDS --, and `x.emit(rng, first_output)` (the current order, each value written once).  A NaN enters as
     +inf.  More than 32 slots per lane (N > 32 W), or W = 1: every lane holds the whole sample as before, so any N compiles.
-    n_stats <= 16."""
+    n_stats <= 16.
+
+    Sums and two-sample distances (csrc/sample_reduce.hpp).  The sum is ONE definition, the balanced binary tree over the
+    element's index (neighbours first, padded with +0.0 to a power of two): `sabc::tree_sum(x, n)` and `sabc::tree_sum(n, g)`
+    (g(i) -> double) for an array, `x.sum(g)`, `x.max(g)`, `x.min(g)` with g(i, value) -> double, `x.sum()`, `x.mean()` and
+    `x.moments(mean, var)` (two passes, var over N - 1) for a `Sample` -- i the draw index before `x.sort()`, the 0-based rank
+    after it; each lane adds its own slots, the team follows with a butterfly over DPP, every lane gets the value.  After the
+    sort all forms give the same bits, whatever the team's width; before it a team sums in the layout of its draws (the same
+    value up to rounding).  Against an ASCENDING data segment `seg`: `sabc::count_less(v, seg)` and
+    `sabc::count_less_equal(v, seg)` (#{j: y_j < v}, <= v; a binary search without a data-dependent branch, a NaN v as +inf),
+    and after `x.sort()` `x.wasserstein1(seg)` = sum_i |x_(i) - y_i| / N and `x.wasserstein2_squared(seg)` (data_len(seg) == N) and
+    `x.ks(seg)`, the Kolmogorov-Smirnov distance for any data_len(seg) >= 1 (N data_len(seg) < 2^53; exact for distinct sample
+    values, with r equal ones at most (r - 1) / N above).  `GandKSample` is the shipped model on them."""
     model_id = _lib.MODEL_USER
 
     def __init__(self, hip_source: str, n_para: int, n_stats: int, params=(), data=None, data_names=None, n_outputs=None,
@@ -506,3 +518,50 @@ class GandKQuantiles(DeviceSource):
             raise ValueError(f"this model was made for {self.n_stats} quantiles (its n_stats), got {len(segments[0])}")
         if not np.all((segments[0] >= 0.0) & (segments[0] <= 1.0)):
             raise ValueError("probs are probabilities: every value in [0, 1]")
+
+
+class GandKSample(DeviceSource):
+    """g-and-k -- the model of `GandKQuantiles`, theta = (A, B, g, k) -- compared with the observed sample as a whole, the
+    usual ABC treatment of it: `distance` = "wasserstein" (rho = sum_i |x_(i) - y_(i)| / n between the sorted samples, the
+    1-Wasserstein distance of two samples of one length), "ks" (Kolmogorov-Smirnov, sup_t |F_x(t) - F_y(t)|; any two lengths), or
+    both names in a sequence: one statistic per name, in the order given.  `y_obs` is ONE data segment, kept sorted -- the
+    class sorts what it is constructed with; another sample of the same length is another `SabcHandle.set_data` or
+    `sabc(model, prior, y_obs=np.sort(y))`, never another compilation --; `n_draws` (default: len(y_obs); with "wasserstein" it
+    must be) and `c` are params.  Source: device_sources/gk_sample.hip on csrc/sample_reduce.hpp: `sabc::tree_sum`, the sum as a
+    balanced tree over the rank, and `sabc::count_less` / `sabc::count_less_equal`, branch-free binary searches in the observed
+    sample.  `team_lanes` = 1, 4 or 16: the same through `sabc::Sample<n_draws, W>` (`wasserstein1`, `ks`) -- every lane compares
+    the ranks it holds after the sort with the observations beside them; the results are the default form's bit for bit.
+    Outputs: the sorted sample, as `GandKQuantiles`."""
+    DISTANCES = ("wasserstein", "ks")
+    MAX_DRAWS = 1024                 # the sample is 8 n_draws bytes of private memory per lane
+
+    def __init__(self, y_obs, distance=("wasserstein", "ks"), n_draws=None, c=0.8, team_lanes=None, data_names=("y_obs",)):
+        names = (distance,) if isinstance(distance, str) else tuple(distance)
+        if not names or len(set(names)) != len(names) or any(d not in self.DISTANCES for d in names):
+            raise ValueError(f"distance is one of {self.DISTANCES!r} or both, each once, got {distance!r}")
+        y_obs = np.sort(_segment(y_obs))
+        if len(y_obs) < 1:
+            raise ValueError("y_obs is one segment of at least one value")
+        if n_draws is None:
+            n_draws = len(y_obs)
+        if isinstance(n_draws, bool) or int(n_draws) != n_draws or not 1 <= int(n_draws) <= self.MAX_DRAWS:
+            raise ValueError(f"n_draws must be an integer in 1..{self.MAX_DRAWS}, got {n_draws!r}")
+        self.distance, self.n_draws, self.c = names, int(n_draws), float(c)
+        head = f"#define GKS_N_DRAWS {self.n_draws}\n" + "".join(f"#define GKS_{d.upper()} {j}\n" for j, d in enumerate(names))
+        team = "" if team_lanes is None else "#define GKS_TEAM 1\n"
+        super().__init__(head + team + device_source_text("gk_sample"), 4, len(names), [self.n_draws, self.c], data=[y_obs],
+                         data_names=data_names, n_outputs=self.n_draws, team_lanes=team_lanes)
+
+    def validate_data(self, segments):
+        # the source reads y[i] for every i < n_draws ("wasserstein") and searches an ascending y ("ks")
+        if len(segments) != 1 or len(segments[0]) < 1:
+            raise ValueError("y_obs is one segment of at least one value")
+        y = segments[0]
+        if not np.all(np.isfinite(y)):
+            raise ValueError("y_obs must be finite")
+        if np.any(np.diff(y) < 0):
+            raise ValueError("y_obs must be ascending: give np.sort(y_obs) (the constructor sorts what it is given)")
+        if "wasserstein" in self.distance and len(y) != self.n_draws:
+            raise ValueError(f'distance "wasserstein" compares rank with rank: len(y_obs) = {len(y)} must equal n_draws = {self.n_draws}')
+        if self.n_draws * len(y) >= 2 ** 53:
+            raise ValueError(f"n_draws * len(y_obs) must stay below 2^53 (the Kolmogorov-Smirnov counts are exact up to there), got {self.n_draws} * {len(y)}")
