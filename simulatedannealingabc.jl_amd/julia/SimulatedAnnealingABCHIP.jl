@@ -20,7 +20,7 @@ import Dates
 import Base: show
 
 export sabc, update_population!, RandomWalk, DifferentialEvolution, StretchMove,
-       DeviceDistance, GaussianIID, Gaussian2D, GandK, LotkaVolterra, DeviceSource, StochasticSIR, LotkaVolterraF32, NormalMoments, StochasticSIRSeries, GandKQuantiles, GandKSample, SourcePrior,
+       DeviceDistance, GaussianIID, Gaussian2D, GandK, LotkaVolterra, DeviceSource, StochasticSIR, LotkaVolterraF32, NormalMoments, StochasticSIRSeries, GandKQuantiles, GandKSample, GandKSampleF32, SourcePrior,
        comm_unique_id, simulate_outputs, posterior_predictive
 
 const libsabc = get(ENV, "SABC_HIP_LIB", joinpath(@__DIR__, "..", "libsabc_hip.so"))
@@ -322,14 +322,28 @@ name in the order given.  One data segment, `y_obs`, kept sorted (the constructo
 ascending).  A `DeviceSource` of device_sources/gk_sample.hip on `sabc::tree_sum`, `sabc::count_less` and `sabc::count_less_equal`
 (csrc/sample_reduce.hpp); `team_lanes` = 1, 4 or 16: the same through `sabc::Sample` (`wasserstein1`, `ks`), the same bits.
 """
-function GandKSample(y_obs; distance=(:wasserstein, :ks), n_draws::Integer=length(y_obs), c=0.8, team_lanes=nothing)
+GandKSample(y_obs; distance=(:wasserstein, :ks), n_draws::Integer=length(y_obs), c=0.8, team_lanes=nothing) =
+    gk_sample_source("gk_sample.hip", team_lanes === nothing ? "" : "#define GKS_TEAM 1\n", y_obs, distance, n_draws, c, team_lanes)
+"""
+    GandKSampleF32(y_obs; distance=(:wasserstein, :ks), n_draws=length(y_obs), c=0.8, team_lanes=4)
+
+`GandKSample` with a binary32 sample: the stream's binary32 normals, four per Philox block, the f64 g-and-k transform of the widened
+normal rounded to binary32 once, kept and sorted as floats in a `sabc::SampleF32` (csrc/team_sample_f32.hpp); both distances
+accumulate in Float64 against `y_obs`, which stays Float64.  A `DeviceSource` of device_sources/gk_sample_f32.hip, which has the
+team-aware form only: `team_lanes` = 1, 4 or 16 (`nothing`: use `GandKSample`), the same bits for the three.
+"""
+function GandKSampleF32(y_obs; distance=(:wasserstein, :ks), n_draws::Integer=length(y_obs), c=0.8, team_lanes=4)
+    team_lanes === nothing &&
+        throw(ArgumentError("team_lanes is 1, 4 or 16: GandKSampleF32 has the team-aware form only; the plain-array form is GandKSample"))
+    gk_sample_source("gk_sample_f32.hip", "", y_obs, distance, n_draws, c, team_lanes)
+end
+function gk_sample_source(file, team, y_obs, distance, n_draws, c, team_lanes)
     names = distance isa Union{Symbol,String} ? (Symbol(distance),) : Tuple(Symbol(d) for d in distance)
     (!isempty(names) && allunique(names) && all(d -> d in (:wasserstein, :ks), names)) ||
         throw(ArgumentError("distance is :wasserstein, :ks or both, each once"))
     1 <= n_draws <= 1024 || throw(ArgumentError("n_draws must be in 1..1024"))
-    text = read(joinpath(@__DIR__, "..", "device_sources", "gk_sample.hip"), String)
+    text = read(joinpath(@__DIR__, "..", "device_sources", file), String)
     head = "#define GKS_N_DRAWS $(n_draws)\n" * join("#define GKS_$(uppercase(String(d))) $(j - 1)\n" for (j, d) in enumerate(names))
-    team = team_lanes === nothing ? "" : "#define GKS_TEAM 1\n"
     rank_with_rank = :wasserstein in names
     DeviceSource(head * team * text, 4, length(names); params=Float64[n_draws, c], data=(sort(data_segment(y_obs)),), data_names=(:y_obs,),
                  validate=segs -> check_sample_data(segs, Int(n_draws), rank_with_rank), team_lanes=team_lanes)

@@ -231,7 +231,14 @@ class DeviceSource(DeviceDistance):
     `sabc::count_less_equal(v, seg)` (#{j: y_j < v}, <= v; a binary search without a data-dependent branch, a NaN v as +inf),
     and after `x.sort()` `x.wasserstein1(seg)` = sum_i |x_(i) - y_i| / N and `x.wasserstein2_squared(seg)` (data_len(seg) == N) and
     `x.ks(seg)`, the Kolmogorov-Smirnov distance for any data_len(seg) >= 1 (N data_len(seg) < 2^53; exact for distinct sample
-    values, with r equal ones at most (r - 1) / N above).  `GandKSample` is the shipped model on them."""
+    values, with r equal ones at most (r - 1) / N above).  `GandKSample` is the shipped model on them.
+
+    `sabc::SampleF32<N, W> x` (csrc/team_sample_f32.hpp) is `Sample` for binary32 values, for simulators whose noise needs no
+    more: `x.fill_normals(rng, f)` with f(float) -> float takes the stream's binary32 normals, four per block (the
+    ceil(N / 4) blocks of `rng.for_quads_f32`), a slot is one register and a cross-lane exchange one word; `x.drawn(i)`,
+    `x.at(i)` and `x.order_statistic(rank)` return float, `x.quantile(p)` double, `x.emit` writes (double)value; the
+    reductions and distances above take g(i, float value) -> double and accumulate in double -- the same canonical tree, the
+    same bits for every width.  `GandKSampleF32` is the shipped model on it."""
     model_id = _lib.MODEL_USER
 
     def __init__(self, hip_source: str, n_para: int, n_stats: int, params=(), data=None, data_names=None, n_outputs=None,
@@ -534,6 +541,8 @@ class GandKSample(DeviceSource):
     Outputs: the sorted sample, as `GandKQuantiles`."""
     DISTANCES = ("wasserstein", "ks")
     MAX_DRAWS = 1024                 # the sample is 8 n_draws bytes of private memory per lane
+    SOURCE = "gk_sample"             # device_sources/<SOURCE>.hip ...
+    TEAM_DEFINE = "#define GKS_TEAM 1\n"      # ... and what selects its team-aware form
 
     def __init__(self, y_obs, distance=("wasserstein", "ks"), n_draws=None, c=0.8, team_lanes=None, data_names=("y_obs",)):
         names = (distance,) if isinstance(distance, str) else tuple(distance)
@@ -548,8 +557,8 @@ class GandKSample(DeviceSource):
             raise ValueError(f"n_draws must be an integer in 1..{self.MAX_DRAWS}, got {n_draws!r}")
         self.distance, self.n_draws, self.c = names, int(n_draws), float(c)
         head = f"#define GKS_N_DRAWS {self.n_draws}\n" + "".join(f"#define GKS_{d.upper()} {j}\n" for j, d in enumerate(names))
-        team = "" if team_lanes is None else "#define GKS_TEAM 1\n"
-        super().__init__(head + team + device_source_text("gk_sample"), 4, len(names), [self.n_draws, self.c], data=[y_obs],
+        team = "" if team_lanes is None else self.TEAM_DEFINE
+        super().__init__(head + team + device_source_text(self.SOURCE), 4, len(names), [self.n_draws, self.c], data=[y_obs],
                          data_names=data_names, n_outputs=self.n_draws, team_lanes=team_lanes)
 
     def validate_data(self, segments):
@@ -565,3 +574,22 @@ class GandKSample(DeviceSource):
             raise ValueError(f'distance "wasserstein" compares rank with rank: len(y_obs) = {len(y)} must equal n_draws = {self.n_draws}')
         if self.n_draws * len(y) >= 2 ** 53:
             raise ValueError(f"n_draws * len(y_obs) must stay below 2^53 (the Kolmogorov-Smirnov counts are exact up to there), got {self.n_draws} * {len(y)}")
+
+
+class GandKSampleF32(GandKSample):
+    """`GandKSample` with a binary32 sample (device_sources/gk_sample_f32.hip on `sabc::SampleF32<n_draws, W>`,
+    csrc/team_sample_f32.hpp): the normals are the stream's binary32 draws, four per Philox block (|z| <= 6.7637, where the f64
+    draws reach 8.57), the g-and-k transform is the f64 one applied to the widened normal, and its result is rounded to binary32
+    once; the team keeps and sorts floats -- a register per slot, one word per cross-lane exchange -- and both distances
+    accumulate in float64 against `y_obs`, which stays float64.  Another stream than `GandKSample`'s: the same model, not the
+    same draws.  `team_lanes` = 1, 4 or 16 lanes per particle, the same bits for the three; the source has the team-aware form
+    only, so None is refused (`GandKSample` has the plain-array form).  Arguments, their checks, data and outputs are
+    `GandKSample`'s; the outputs are binary32 values."""
+    SOURCE = "gk_sample_f32"
+    TEAM_DEFINE = ""                 # the text is team-aware throughout
+
+    def __init__(self, y_obs, distance=("wasserstein", "ks"), n_draws=None, c=0.8, team_lanes=4, data_names=("y_obs",)):
+        if team_lanes is None:
+            raise ValueError("team_lanes is 1, 4 or 16: GandKSampleF32 has the team-aware form only (sabc::SampleF32); the plain-array "
+                             "form is GandKSample(..., team_lanes=None)")
+        super().__init__(y_obs, distance=distance, n_draws=n_draws, c=c, team_lanes=team_lanes, data_names=data_names)
