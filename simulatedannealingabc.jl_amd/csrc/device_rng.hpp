@@ -1009,3 +1009,4 @@ __device__ __forceinline__ void emit(NormalStream &rng, const long long i, const
 
 #include "team_sample.hpp"     // sabc::Sample<N, W>: a sample spread over the lanes of a team (uses NormalStream, team_pick and emit above)
 #include "team_sample_f32.hpp" // sabc::SampleF32<N, W>: its binary32 twin, four normals per block (f32::box_muller_quad, team_pick_f32)
+#include "team_series.hpp"     // sabc::Series<N, W>: a time series in time order over the team, lags through DPP (uses the above)

@@ -1,0 +1,356 @@
+// team_series.hpp -- sabc::Series<N, W>: one particle's time series x_0 .. x_{N-1} of doubles, in time order, on the W lanes that
+// run the particle; element t meets element t - L across the lanes of the team.
+//
+// team_sample.hpp holds a SAMPLE: what it computes is symmetric in its elements (order statistics, distances between sorted
+// samples), and before the sort an element lies where its Philox block was generated.  A series is compared through lagged
+// summaries -- autocovariances of an MA(q) or AR model, the lag statistics of Ricker or Lotka-Volterra --, so it lies in time
+// order from the start, in the layout Sample has AFTER its sort:
+//
+//   M = teamsort::slots(N, W); time t on lane t / M in slot t mod M: position p = q M + r.  Positions >= N hold 0.0 and take part
+//   in nothing.  Spread over the team when teamsort::spread(N, W); else (W = 1, or M > 32) REPLICATED, a plain double x[N] per
+//   lane with the same results, so any N compiles for any W.
+//
+//   fill_normals: lane q generates the blocks q M / 2 + a, a < M / 2, that exist (< ceil(N / 2)) and keeps both normals of each:
+//   block b IS normals 2 b and 2 b + 1, so they land in slots 2 a and 2 a + 1 -- nothing moves between lanes.  (Sample deals its
+//   blocks round-robin, block b to lane b mod W; here a lane's blocks are consecutive.)  The stream advances by ceil(N / 2): the
+//   blocks and values a lane gets from rng.for_pairs plus an odd last draw, which is what the replicated form does.
+//
+//   lag<L>: position p reads position p - L.  With L = a M + b, b < M, slot r reads slot r - b of lane q - a where r >= b, and
+//   slot r - b + M of lane q - a - 1 where r < b: source slot and lane distance are compile-time constants per slot, at most
+//   two distances per L (series::lag_source).  Distance 0 is a register move; distance d one row_shr:d DPP move per 32-bit
+//   half -- a quad is aligned inside its row of 16, so the same instruction serves W = 4 --, and the lanes q < d, whose source
+//   would lie before the series (or in the neighbouring team), take `before`.  p < L holds exactly on those lanes.
+//
+//   Reductions: the canonical sum of sample_reduce.hpp over the time index -- a lane adds the tree of its own M slots, the team
+//   follows with the xor_lane butterfly, then finish_sum.  Position equals index for every W, so sum, lagged_sum and
+//   autocovariance give the same bits for 1, 4 and 16 lanes, for the replicated store and for the NumPy restatement, always (a
+//   Sample only after its sort).  No LDS memory, no barrier, no atomic; a read-out returns the same value on every lane.
+//
+// A series is not sorted, so there is no NaN policy: values pass through unchanged.
+//
+// Out of scope: prefix scans (cumsum, AR recurrences), whose rounding depends on the order of association and so on W; a
+// binary32 twin; lags between two series other than through lag<L>() followed by zip.
+//
+// The layout, the lag schedule and the block ownership are constexpr and compile with a plain C++ compiler, as
+// teamsort::step_at does; tests/team_series/check_series.cpp runs them on plain arrays of W M positions.
+#pragma once
+#include "team_sample.hpp"
+
+namespace sabc {
+namespace series {
+
+constexpr int time_lane(int t, int m) { return t / m; }
+constexpr int time_slot(int t, int m) { return t & (m - 1); }
+constexpr int time_of(int lane, int slot, int m) { return lane * m + slot; }
+
+// slot r of lane q takes, for lag l, slot `slot` of lane q - dist (dist may reach w: then no lane has a source)
+struct Source {
+  int slot, dist;
+};
+constexpr Source lag_source(int r, int l, int m) {
+  return r >= (l & (m - 1)) ? Source{r - (l & (m - 1)), l / m} : Source{r - (l & (m - 1)) + m, l / m + 1};
+}
+
+// fill_normals: the a-th block of lane q (a < m / 2), and whether it is one of the stream's ceil(n / 2)
+constexpr int block_of(int lane, int a, int m) { return lane * (m / 2) + a; }
+constexpr bool owns_block(int lane, int a, int n, int m) { return block_of(lane, a, m) < teamsort::blocks(n); }
+
+// (x - c)(y - c) rounded on its own: a product that the canonical tree's additions cannot fuse with, so every width and the NumPy
+// restatement agree to the bit.  The pragma is what the language offers; a compiler told -ffp-contract=fast (the run-time
+// compiler is) fuses whatever it sees regardless, so on the device the product also passes through an empty asm, behind which
+// the compiler sees no product.
+SABC_SORT_HD double rounded_product(const double a, const double b) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  double p = a * b;
+#if defined(__HIP_DEVICE_COMPILE__)
+  asm("" : "+v"(p));
+#endif
+  return p;
+}
+
+// ---- the schedule on plain arrays of w m positions (the CPU proof; the definitions the device's members are held to) ----
+// out[p] = in[p - l] where a source exists, `before` on the lanes in front of it, 0.0 at positions >= n
+SABC_SORT_HD void run_lag(const int w, const int m, const int n, const int l, const double before, const double *in, double *out) {
+  for (int q = 0; q < w; ++q)
+    for (int r = 0; r < m; ++r) {
+      const Source s = lag_source(r, l, m);
+      const double v = q < s.dist ? before : in[time_of(q - s.dist, s.slot, m)];
+      out[time_of(q, r, m)] = time_of(q, r, m) < n ? v : 0.0;
+    }
+}
+// the team's sum of the terms at its w m positions: every lane the tree of its own slots, then the butterfly over the lane
+// distances 1, 2, .., w / 2, then finish_sum; lane 0's value (sums[] of w entries is scratch: every lane ends with the same bits)
+SABC_SORT_HD double run_team_sum(const int w, const int m, double *term, double *sums) {
+  for (int q = 0; q < w; ++q) {
+    for (int d = 1; d < m; d <<= 1)
+      for (int r = 0; r < m; r += 2 * d) term[q * m + r] = term[q * m + r] + term[q * m + r + d];
+    sums[q] = term[q * m];
+  }
+  for (int d = 1; d < w; d <<= 1)
+    for (int q = 0; q < w; ++q)
+      if (!(q & d)) sums[q] = sums[q | d] = sums[q] + sums[q | d];
+  return reduce::finish_sum(sums[0]);
+}
+// lagged_sum<L>(g, first) on a plain array x of w m positions, through run_lag and run_team_sum (lagged, term: w m entries each)
+template <class G>
+SABC_SORT_HD double run_lagged_sum(const int w, const int m, const int n, const int l, const int first, G &&g, const double *x,
+                                   double *lagged, double *term, double *sums) {
+  if (l > 0) run_lag(w, m, n, l, 0.0, x, lagged);
+  for (int p = 0; p < w * m; ++p) term[p] = p < n && p >= first + l ? g(p, x[p], l > 0 ? lagged[p] : x[p]) : 0.0;
+  return run_team_sum(w, m, term, sums);
+}
+
+}  // namespace series
+}  // namespace sabc
+
+#if defined(__HIPCC__) || defined(__HIPCC_RTC__)
+// ---- the device's half: included from the end of device_rng.hpp, behind team_sample.hpp whose select_slot, xor_lane and team_add
+// it uses ----
+namespace sabc {
+namespace series {
+
+// v from lane - D of the row of 16 (control_kernel.hpp: dpp_row_shr has this shape); 0 where the row has no such lane
+template <int D>
+__device__ __forceinline__ double row_shr(const double v) {
+  static_assert(D >= 1 && D <= 15, "a lane of the own row of 16");
+  const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), 0x110 + D, 0xF, 0xF, true);
+  const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), 0x110 + D, 0xF, 0xF, true);
+  return __hiloint2double(hi, lo);
+}
+
+// ---- spread over the team ----
+template <int N, int W, bool SPREAD>
+struct SeriesStore {
+  static constexpr int M = teamsort::slots(N, W);
+  static_assert(W == 4 || W == 16, "a quad or a row of 16 lanes");
+  using Sums = teamsort::SampleStore<N, W, true>;      // team_add, team_extreme: the butterflies of Sample
+  double v[M];
+
+  static __device__ __forceinline__ int lane() { return (int)(threadIdx.x & (unsigned)(W - 1)); }
+
+  template <class F>
+  __device__ __forceinline__ void fill_normals(NormalStream &rng, F &&f) {
+    const int q = lane();
+#pragma unroll
+    for (int a = 0; a < M / 2; ++a) {
+      v[2 * a] = v[2 * a + 1] = 0.0;
+      if (owns_block(0, a, N, M)) {                      // (a constant: some lane of the team has an a-th block)
+        double z0, z1;
+        box_muller(stream_block(rng.seed, rng.pid, rng.purpose, rng.iter, rng.k + (uint32_t)block_of(q, a, M)), z0, z1);
+        const int t = 2 * block_of(q, a, M);
+        if (t < N) v[2 * a] = f(t, z0);
+        if (t + 1 < N) v[2 * a + 1] = f(t + 1, z1);
+      }
+    }
+    rng.k += (uint32_t)teamsort::blocks(N);
+  }
+  template <class G>
+  __device__ __forceinline__ void fill(G &&g) {
+    const int q = lane();
+#pragma unroll
+    for (int r = 0; r < M; ++r) {
+      v[r] = 0.0;
+      if (time_of(q, r, M) < N) v[r] = g(time_of(q, r, M));
+    }
+  }
+  template <class G>
+  __device__ __forceinline__ void map(G &&g) {
+    const int q = lane();
+#pragma unroll
+    for (int r = 0; r < M; ++r)
+      if (time_of(q, r, M) < N) v[r] = g(time_of(q, r, M), v[r]);
+  }
+  template <class G>
+  __device__ __forceinline__ void zip(const SeriesStore &other, G &&g) {
+    const int q = lane();
+#pragma unroll
+    for (int r = 0; r < M; ++r)
+      if (time_of(q, r, M) < N) v[r] = g(time_of(q, r, M), v[r], other.v[r]);
+  }
+  __device__ __forceinline__ double at(const int t) const {
+    return team_pick<W>(teamsort::select_slot<M>(v, time_slot(t, M)), (uint32_t)time_lane(t, M));
+  }
+  __device__ __forceinline__ void emit(NormalStream &rng, const long long first_output, const int first) const {
+    if (!emitting(rng)) return;
+    const int q = lane();
+#pragma unroll
+    for (int r = 0; r < M; ++r) {
+      const int t = time_of(q, r, M);
+      if (t < N && t >= first) sabc::emit(rng, first_output + (t - first), v[r]);
+    }
+  }
+
+  template <int L, int R>
+  __device__ __forceinline__ double lagged_slot(const int q, const double before) const {
+    constexpr Source s = lag_source(R, L, M);
+    double x;
+    if constexpr (s.dist == 0) x = v[s.slot];
+    else if constexpr (s.dist >= W) x = before;
+    else {
+      // the move first, by every lane of the team, the choice after it: inside the conditional's arm it would run with the lanes
+      // q < dist switched off, and a DPP move reads 0 from a lane that is
+      const double shifted = row_shr<s.dist>(v[s.slot]);
+      x = q < s.dist ? before : shifted;
+    }
+    if constexpr (time_of(W - 1, R, M) >= N) x = time_of(q, R, M) < N ? x : 0.0;
+    return x;
+  }
+  template <int L, int... R>
+  __device__ __forceinline__ void lag_into(SeriesStore &out, const double before, sortnet::seq<R...>) const {
+    const int q = lane();
+    ((out.v[R] = lagged_slot<L, R>(q, before)), ...);
+  }
+  template <int L>
+  __device__ __forceinline__ void lag_store(SeriesStore &out, const double before) const {
+    lag_into<L>(out, before, typename sortnet::make_seq<M>::type{});
+  }
+
+  // the canonical sum of g(t, x_t, x_{t-L}) over first + L <= t < N, +0.0 elsewhere
+  template <int L, class G>
+  __device__ __forceinline__ double lagged_sum_store(G &&g, const int first) const {
+    const int q = lane();
+    double term[M];
+    if constexpr (L == 0) {
+#pragma unroll
+      for (int r = 0; r < M; ++r) {
+        const int t = time_of(q, r, M);
+        term[r] = t < N && t >= first ? g(t, v[r], v[r]) : 0.0;
+      }
+    } else {
+      SeriesStore back;
+      lag_store<L>(back, 0.0);
+#pragma unroll
+      for (int r = 0; r < M; ++r) {
+        const int t = time_of(q, r, M);
+        term[r] = t < N && t >= first + L ? g(t, v[r], back.v[r]) : 0.0;
+      }
+    }
+    return reduce::finish_sum(Sums::team_add(reduce::lane_tree(term)));
+  }
+  template <bool MAX, class G>
+  __device__ __forceinline__ double extreme(G &&g) const {
+    const int q = lane();
+    double s = MAX ? -sortnet::inf_(0.0) : sortnet::inf_(0.0);
+#pragma unroll
+    for (int r = 0; r < M; ++r) {
+      const int t = time_of(q, r, M);
+      if (t < N) s = MAX ? sortnet::max_(s, g(t, v[r])) : sortnet::min_(s, g(t, v[r]));
+    }
+    return Sums::template team_extreme<MAX>(s);
+  }
+};
+
+// ---- replicated: a lane per particle, or a series too long for the team's registers ----
+template <int N, int W>
+struct SeriesStore<N, W, false> {
+  static_assert(W == 1 || W == 4 || W == 16, "a lane, a quad or a row of 16 lanes");
+  double x[N];
+
+  template <class F>
+  __device__ __forceinline__ void fill_normals(NormalStream &rng, F &&f) {
+    int at_ = 0;
+    rng.for_pairs(N >> 1, [&](const double z0, const double z1) {
+      x[at_] = f(at_, z0);
+      x[at_ + 1] = f(at_ + 1, z1);
+      at_ += 2;
+    });
+    if (N & 1) {
+      double z0, z1;
+      rng.pair(z0, z1);
+      x[N - 1] = f(N - 1, z0);
+    }
+  }
+  template <class G>
+  __device__ __forceinline__ void fill(G &&g) {
+    for (int t = 0; t < N; ++t) x[t] = g(t);
+  }
+  template <class G>
+  __device__ __forceinline__ void map(G &&g) {
+    for (int t = 0; t < N; ++t) x[t] = g(t, x[t]);
+  }
+  template <class G>
+  __device__ __forceinline__ void zip(const SeriesStore &other, G &&g) {
+    for (int t = 0; t < N; ++t) x[t] = g(t, x[t], other.x[t]);
+  }
+  __device__ __forceinline__ double at(const int t) const { return x[t]; }
+  __device__ __forceinline__ void emit(NormalStream &rng, const long long first_output, const int first) const {
+    if (!emitting(rng) || (threadIdx.x & (unsigned)(W - 1)) != 0) return;
+    for (int t = first > 0 ? first : 0; t < N; ++t) sabc::emit(rng, first_output + (t - first), x[t]);
+  }
+  template <int L>
+  __device__ __forceinline__ void lag_store(SeriesStore &out, const double before) const {
+    for (int t = 0; t < N; ++t) out.x[t] = t >= L ? x[t >= L ? t - L : 0] : before;
+  }
+  template <int L, class G>
+  __device__ __forceinline__ double lagged_sum_store(G &&g, const int first) const {
+    return reduce::tree_sum_of(N, [&](const int t) { return t >= first + L ? g(t, x[t], x[t >= L ? t - L : 0]) : 0.0; });
+  }
+  template <bool MAX, class G>
+  __device__ __forceinline__ double extreme(G &&g) const {
+    double s = MAX ? -sortnet::inf_(0.0) : sortnet::inf_(0.0);
+    for (int t = 0; t < N; ++t) s = MAX ? sortnet::max_(s, g(t, x[t])) : sortnet::min_(s, g(t, x[t]));
+    return s;
+  }
+};
+
+}  // namespace series
+
+// One particle's series of N doubles in time order on the W = 1 | 4 | 16 lanes that run the particle (a simulator from source
+// gets W as the template argument of sabc_user_simulate_team<W>).  All lanes of a team make the same calls in the same order;
+// a read-out returns the same value on every lane of the team.
+//   fill_normals(rng, f): x_t = f(t, normal t of the stream), ceil(N / 2) whole blocks consumed; fill(g): x_t = g(t);
+//   map(g): x_t <- g(t, x_t); zip(other, g): x_t <- g(t, x_t, other_t), in-lane; at(t): x_t, t uniform over the team;
+//   emit(rng, first_output, first = 0): x_t, t >= first, to output first_output + t - first, each value written once.
+//   lag<L>(before = 0.0), 1 <= L < N: the series whose element t is x_{t-L}, `before` for t < L.
+//   lagged_sum<L>(g, first = 0): the canonical sum over t = 0 .. N-1 of g(t, x_t, x_{t-L}) for t >= first + L, +0.0 otherwise.
+//   autocovariance<L>(center = 0.0, first = 0), 0 <= L < N: that sum of (x_t - c)(x_{t-L} - c), each product rounded on its own
+//   (series::rounded_product), divided by N - first.
+//   sum(g), max(g), min(g) over g(t, x_t); sum(), mean(); moments(mean, var): Sample's definitions over the time index.
+// Values pass through unchanged: no NaN policy.  The same bits for every W.
+template <int N, int W>
+struct Series : series::SeriesStore<N, W, teamsort::spread(N, W)> {
+  static_assert(N >= 1, "a series holds at least one value");
+  static constexpr int size = N, lanes = W;
+  static constexpr bool spread = teamsort::spread(N, W);
+  using Store = series::SeriesStore<N, W, teamsort::spread(N, W)>;
+
+  __device__ __forceinline__ void emit(NormalStream &rng, const long long first_output, const int first = 0) const {
+    Store::emit(rng, first_output, first);
+  }
+  template <int L>
+  __device__ __forceinline__ Series lag(const double before = 0.0) const {
+    static_assert(L >= 1 && L < N, "1 <= L < N");
+    Series out;
+    Store::template lag_store<L>(out, before);
+    return out;
+  }
+  template <int L, class G>
+  __device__ __forceinline__ double lagged_sum(G &&g, const int first = 0) const {
+    static_assert(L >= 1 && L < N, "1 <= L < N");
+    return Store::template lagged_sum_store<L>(g, first);
+  }
+  template <int L>
+  __device__ __forceinline__ double autocovariance(const double center = 0.0, const int first = 0) const {
+    static_assert(L >= 0 && L < N, "0 <= L < N");
+    return Store::template lagged_sum_store<L>([&](const int, const double a, const double b) {
+      return series::rounded_product(a - center, b - center);
+    }, first) / (double)(N - first);
+  }
+  template <class G> __device__ __forceinline__ double sum(G &&g) const {
+    return Store::template lagged_sum_store<0>([&](const int t, const double a, const double) { return g(t, a); }, 0);
+  }
+  template <class G> __device__ __forceinline__ double max(G &&g) const { return Store::template extreme<true>(g); }
+  template <class G> __device__ __forceinline__ double min(G &&g) const { return Store::template extreme<false>(g); }
+  __device__ __forceinline__ double sum() const { return sum([](const int, const double x) { return x; }); }
+  __device__ __forceinline__ double mean() const { return sum() / (double)N; }
+  __device__ __forceinline__ void moments(double &mean_out, double &var_out) const {
+    const double m = mean();
+    mean_out = m;
+    var_out = N > 1 ? sum([&](const int, const double x) { return (x - m) * (x - m); }) / (double)(N > 1 ? N - 1 : 1) : 0.0;
+  }
+};
+
+}  // namespace sabc
+#endif

@@ -20,7 +20,7 @@ import Dates
 import Base: show
 
 export sabc, update_population!, RandomWalk, DifferentialEvolution, StretchMove,
-       DeviceDistance, GaussianIID, Gaussian2D, GandK, LotkaVolterra, DeviceSource, StochasticSIR, LotkaVolterraF32, NormalMoments, StochasticSIRSeries, GandKQuantiles, GandKSample, GandKSampleF32, SourcePrior,
+       DeviceDistance, GaussianIID, Gaussian2D, GandK, LotkaVolterra, DeviceSource, StochasticSIR, LotkaVolterraF32, NormalMoments, StochasticSIRSeries, GandKQuantiles, GandKSample, GandKSampleF32, MA2, SourcePrior,
        comm_unique_id, simulate_outputs, posterior_predictive
 
 const libsabc = get(ENV, "SABC_HIP_LIB", joinpath(@__DIR__, "..", "libsabc_hip.so"))
@@ -353,6 +353,41 @@ check_sample_data(segs, n_draws, rank_with_rank) =
     (length(segs) == 1 && length(segs[1]) >= 1 && all(isfinite, segs[1]) && issorted(segs[1]) &&
      (!rank_with_rank || length(segs[1]) == n_draws) && n_draws * length(segs[1]) < 2^53) ||
     throw(ArgumentError("y_obs is one ascending segment of finite values" * (rank_with_rank ? ", $(n_draws) of them (distance :wasserstein)" : "")))
+"""
+    MA2(; acov_obs=nothing, n_obs=100, n_lags=2, team_lanes=nothing)
+    MA2(y_obs; n_lags=2, team_lanes=nothing)
+
+MA(2) with autocovariance summaries (Marin et al. 2012): θ = (θ1, θ2), y_t = e_{t+2} + θ1 e_{t+1} + θ2 e_t for `n_obs` times,
+τ_j = Σ_{t ≥ j} y_t y_{t−j} / n_obs for j = 0 .. `n_lags` (at most 7), ρ_j = |τ_j − acov_obs[j]|.  One data segment, `acov_obs`, of
+`n_lags + 1` finite values; the second method takes it from an observed series (`ma2_autocovariances`: the device's own sum).
+A `DeviceSource` of device_sources/ma2.hip on `sabc::Series` (csrc/team_series.hpp): the innovations in time order over the
+team, `lag<1>`, `lag<2>` and two `zip`s, `autocovariance<j>`.  `team_lanes` = 1, 4 or 16: that many lanes per particle, the same
+bits as the default (`nothing`: a private array per lane).
+"""
+function MA2(; acov_obs=nothing, n_obs::Integer=100, n_lags::Integer=2, team_lanes=nothing)
+    0 <= n_lags <= 7 || throw(ArgumentError("n_lags must be in 0..7"))
+    n_lags < n_obs <= 1022 || throw(ArgumentError("n_obs must be above n_lags and at most 1022"))
+    text = read(joinpath(@__DIR__, "..", "device_sources", "ma2.hip"), String)
+    head = "#define MA2_N_OBS $(n_obs)\n#define MA2_N_LAGS $(n_lags)\n" * (team_lanes === nothing ? "" : "#define MA2_TEAM 1\n")
+    DeviceSource(head * text, 2, Int(n_lags) + 1; params=Float64[n_obs, n_lags], data=acov_obs === nothing ? nothing : (acov_obs,),
+                 data_names=(:acov_obs,), validate=segs -> check_acov_data(segs, Int(n_lags)), team_lanes=team_lanes)
+end
+MA2(y_obs; n_lags::Integer=2, team_lanes=nothing) =
+    MA2(; acov_obs=ma2_autocovariances(data_segment(y_obs), n_lags), n_obs=length(y_obs), n_lags=n_lags, team_lanes=team_lanes)
+# the source reads acov_obs[j] and writes ρ[j] for every j <= n_lags
+check_acov_data(segs, n_lags) = (length(segs) == 1 && length(segs[1]) == n_lags + 1 && all(isfinite, segs[1])) ||
+    throw(ArgumentError("acov_obs is one segment of $(n_lags + 1) finite values"))
+# the canonical sum of csrc/sample_reduce.hpp: the balanced binary tree over the index, padded with +0.0 to a power of two, + 0.0 last
+function tree_sum(s)
+    a = vcat(collect(Float64, s), zeros(nextpow(2, max(length(s), 1)) - length(s)))
+    while length(a) > 1
+        a = a[1:2:end] .+ a[2:2:end]
+    end
+    a[1] + 0.0
+end
+# τ_0 .. τ_n_lags as the device computes them: rounded products, the tree over the innovations' n + 2 times (two leading zeros)
+ma2_autocovariances(y, n_lags) =
+    Float64[tree_sum(vcat(zeros(2 + j), y[(j + 1):end] .* y[1:(end - j)])) / length(y) for j in 0:n_lags]
 """
     SourcePrior(d)
 

@@ -238,7 +238,19 @@ class DeviceSource(DeviceDistance):
     ceil(N / 4) blocks of `rng.for_quads_f32`), a slot is one register and a cross-lane exchange one word; `x.drawn(i)`,
     `x.at(i)` and `x.order_statistic(rank)` return float, `x.quantile(p)` double, `x.emit` writes (double)value; the
     reductions and distances above take g(i, float value) -> double and accumulate in double -- the same canonical tree, the
-    same bits for every width.  `GandKSampleF32` is the shipped model on it."""
+    same bits for every width.  `GandKSampleF32` is the shipped model on it.
+
+    `sabc::Series<N, W> x` (csrc/team_series.hpp) holds a time series x_0 .. x_{N-1} of doubles in time order over the team --
+    time t on lane t / M in slot t mod M, where a `Sample` holds rank t after its sort -- for models compared through lagged
+    summaries: `x.fill_normals(rng, f)` (x_t = f(t, z_t), a lane generating the consecutive blocks of its own times),
+    `x.fill(g)`, `x.map(g)` (x_t <- g(t, x_t)), `x.zip(other, g)` (x_t <- g(t, x_t, other_t)), `x.at(t)`,
+    `x.emit(rng, first_output, first = 0)`, and `x.lag<L>(before = 0.0)` -- the series whose element t is x_{t-L}, `before` for
+    t < L: a register move inside a lane, one row_shr DPP move per 32-bit half between lanes, no LDS.  `x.lagged_sum<L>(g, first = 0)`
+    is the canonical sum of g(t, x_t, x_{t-L}) over t >= first + L, `x.autocovariance<L>(center = 0.0, first = 0)` that sum of
+    (x_t - c)(x_{t-L} - c), each product rounded on its own, over N - first; `sum`, `max`, `min`, `mean`, `moments` as for a
+    `Sample`, over the time index.  Position equals index for every width, so all of them give the same bits for 1, 4 and 16
+    lanes, always.  Values pass through unchanged (no NaN policy: nothing is sorted).  Not there: prefix scans (cumsum, AR
+    recurrences), a binary32 twin.  `MA2` is the shipped model on it."""
     model_id = _lib.MODEL_USER
 
     def __init__(self, hip_source: str, n_para: int, n_stats: int, params=(), data=None, data_names=None, n_outputs=None,
@@ -593,3 +605,79 @@ class GandKSampleF32(GandKSample):
             raise ValueError("team_lanes is 1, 4 or 16: GandKSampleF32 has the team-aware form only (sabc::SampleF32); the plain-array "
                              "form is GandKSample(..., team_lanes=None)")
         super().__init__(y_obs, distance=distance, n_draws=n_draws, c=c, team_lanes=team_lanes, data_names=data_names)
+
+
+def _tree_sum(s):
+    """The canonical sum of csrc/sample_reduce.hpp along the last axis: the balanced binary tree over the index, padded with
+    +0.0 to a power of two, + 0.0 last."""
+    a = np.asarray(s, dtype=np.float64)
+    p = 1
+    while p < a.shape[-1]:
+        p *= 2
+    a = np.concatenate([a, np.zeros(a.shape[:-1] + (p - a.shape[-1],))], axis=-1)
+    while a.shape[-1] > 1:
+        a = a.reshape(a.shape[:-1] + (-1, 2))
+        a = a[..., 0] + a[..., 1]
+    return a[..., 0] + 0.0
+
+
+class MA2(DeviceSource):
+    """MA(2) with autocovariance summaries, the canonical ABC benchmark (Marin, Pudlo, Robert, Ryder 2012): theta = (theta1,
+    theta2), y_t = e_{t+2} + theta1 e_{t+1} + theta2 e_t for t = 0 .. n_obs-1 with e the next n_obs + 2 normals of the particle's
+    stream, tau_j = sum_{t >= j} y_t y_{t-j} / n_obs for j = 0 .. n_lags (n_lags <= 7), rho_j = |tau_j - acov_obs[j]|: n_stats =
+    n_lags + 1.  `acov_obs` is ONE data segment of n_lags + 1 finite values -- another series' autocovariances are another
+    `SabcHandle.set_data` or `sabc(model, prior, acov_obs=...)`, never another compilation --; `n_obs` and `n_lags` are
+    compile-time constants of the source.  `from_observations(y_obs)` computes `acov_obs` from a series with the device's own
+    sum (`autocovariances`), `observe(theta)` lets the device source simulate a series.
+    Source: device_sources/ma2.hip on `sabc::Series<n_obs + 2, W>` (csrc/team_series.hpp): the innovations in time order, y from
+    `lag<1>`, `lag<2>` and two `zip`s with explicit fmas, the summaries `autocovariance<j>`.  `team_lanes` = 1, 4 or 16: the
+    series spread over that many lanes per particle, lags through DPP; None (the default): the same text with a private array per
+    lane.  All forms give the same bits.  Outputs: the series y (`posterior_predictive` gives [n, n_rep, n_obs])."""
+    MAX_LAGS = 7
+    MAX_OBS = 1022                   # the series is 8 (n_obs + 2) bytes of private memory per lane where it is not spread
+
+    def __init__(self, acov_obs=None, n_obs=100, n_lags=2, team_lanes=None, data_names=("acov_obs",)):
+        if isinstance(n_lags, bool) or int(n_lags) != n_lags or not 0 <= int(n_lags) <= self.MAX_LAGS:
+            raise ValueError(f"n_lags must be an integer in 0..{self.MAX_LAGS}, got {n_lags!r}")
+        if isinstance(n_obs, bool) or int(n_obs) != n_obs or not int(n_lags) < int(n_obs) <= self.MAX_OBS:
+            raise ValueError(f"n_obs must be an integer above n_lags = {n_lags} and at most {self.MAX_OBS}, got {n_obs!r}")
+        self.n_obs, self.n_lags = int(n_obs), int(n_lags)
+        head = f"#define MA2_N_OBS {self.n_obs}\n#define MA2_N_LAGS {self.n_lags}\n" + ("" if team_lanes is None else "#define MA2_TEAM 1\n")
+        super().__init__(head + device_source_text("ma2"), 2, self.n_lags + 1, [self.n_obs, self.n_lags],
+                         data=None if acov_obs is None else [_segment(acov_obs)], data_names=data_names, n_outputs=self.n_obs,
+                         team_lanes=team_lanes)
+
+    @staticmethod
+    def autocovariances(y, n_lags=2):
+        """tau_0 .. tau_n_lags of a series (along the last axis) as the device computes them: every product rounded on its own,
+        the canonical sum over the innovations' n_obs + 2 times -- two leading +0.0 terms, which the tree's shape depends on --,
+        divided by n_obs."""
+        y = np.asarray(y, dtype=np.float64)
+        n = y.shape[-1]
+        tau = []
+        for j in range(int(n_lags) + 1):
+            terms = np.zeros(y.shape[:-1] + (n + 2,))
+            terms[..., 2 + j:] = y[..., j:] * y[..., :n - j]
+            tau.append(_tree_sum(terms) / float(n))
+        return np.stack(tau, axis=-1)
+
+    @classmethod
+    def from_observations(cls, y_obs, n_lags=2, team_lanes=None):
+        """The model for an observed series `y_obs`: n_obs = len(y_obs), acov_obs = its autocovariances at lags 0 .. n_lags."""
+        y_obs = _segment(y_obs)
+        return cls(cls.autocovariances(y_obs, n_lags), n_obs=len(y_obs), n_lags=n_lags, team_lanes=team_lanes)
+
+    @classmethod
+    def observe(cls, theta, n_obs=100, seed=None, device=None):
+        """A series of n_obs values made by the device source itself: one forward run at theta = (theta1, theta2) on the
+        predictive stream of particle 0, iteration 0 of `seed`."""
+        from .api import simulate_outputs
+        model = cls(np.zeros(1), n_obs=n_obs, n_lags=0)
+        return simulate_outputs(model, np.asarray(theta, dtype=np.float64).reshape(1, 2), seed=seed, device=device)[0, 0]
+
+    def validate_data(self, segments):
+        # the source reads acov_obs[j] and writes rho[j] for every j <= n_lags
+        if len(segments) != 1 or len(segments[0]) != self.n_lags + 1:
+            raise ValueError(f"acov_obs is one segment of n_lags + 1 = {self.n_lags + 1} values (the autocovariances at lags 0 .. {self.n_lags})")
+        if not np.all(np.isfinite(segments[0])):
+            raise ValueError("acov_obs must be finite")
