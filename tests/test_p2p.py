@@ -40,13 +40,16 @@ def shard_stream(rank):
     return _shard_streams[rank]
 
 
-def run_shards_in_one_process(S, case, alg, prop, n, k, resample, world=2, timeout_ms=None, before_update=None, calls=1):
+def run_shards_in_one_process(S, case, alg, prop, n, k, resample, world=2, timeout_ms=None, before_update=None, calls=1,
+                              delta=None):
     """One host thread + one stream per shard; descriptors exchanged through a Python list.  before_update(rank, handle,
-    call) may tamper with a shard; returns per-rank dicts (or the exception a shard's call raised)."""
+    call) may tamper with a shard; delta: the resampling intensity of every update (None: update's default); returns
+    per-rank dicts (or the exception a shard's call raised)."""
     import torch
     from tests.cases import MODELS, SEED, hip_model_prior, hip_proposal
     d = len(MODELS[case]["prior"])
     descs, out, err = [None] * world, [None] * world, [None] * world
+    upd = {} if delta is None else dict(delta=delta)
     barrier = threading.Barrier(world)
 
     def shard(rank):
@@ -84,7 +87,7 @@ def run_shards_in_one_process(S, case, alg, prop, n, k, resample, world=2, timeo
                     before_update(rank, h, call)
                 t0 = time.perf_counter()
                 try:
-                    h.update(n_simulation=k * n, proposal=hip_proposal(S, prop, d), resample=resample)
+                    h.update(n_simulation=k * n, proposal=hip_proposal(S, prop, d), resample=resample, **upd)
                     res["errors"].append(None)
                 except S.SABCError as e:
                     res["errors"].append(e)
@@ -100,7 +103,7 @@ def run_shards_in_one_process(S, case, alg, prop, n, k, resample, world=2, timeo
                     barrier.wait()                                   # both shards are out of the failed call
                     h.set_population(*before[3])                     # what the wrapper does from the result's own arrays
                     setup()                                          # a fresh peer-to-peer set-up (sequence numbers start over)
-                    h.update(n_simulation=k * n, proposal=hip_proposal(S, prop, d), resample=resample)
+                    h.update(n_simulation=k * n, proposal=hip_proposal(S, prop, d), resample=resample, **upd)
             th, u, rho = h.get_population()
             res.update(theta=th, u=u, rho=rho, eps=h.eps, counters=h.counters, launches=h.kernel_launches - launches0,
                        syncs=h.host_syncs - syncs0, collective_calls=h.collective_calls, comm=h.comm_bytes, hist=h.history)
