@@ -44,6 +44,11 @@
 // same value; no LDS, no barrier, no atomic.  A slot whose element index is >= N adds +0.0 and takes no part in a maximum.
 // After sort() position q M + r holds rank q M + r: in-lane levels are the low bits, the lanes the high bits of the canonical
 // tree over the rank, whatever W is -- the same bits for 1, 4 and 16 lanes and for the replicated store.
+//
+// All of this is written ONCE for the element types double and float: the layout functions take the normals per block, and the
+// device's executor, store, summaries and distances are templates over teamsort::Element<T>, which holds what the type decides
+// (below; Element<float> and what it changes in the paragraphs above: team_sample_f32.hpp).  Sample<N, W> is the instance for
+// doubles.  The team's f64 butterflies (team_add, team_extreme) and the Summaries also serve sabc::Series (team_series.hpp).
 #pragma once
 #include "sample_reduce.hpp"
 #include "sort_network.hpp"
@@ -53,14 +58,17 @@ namespace teamsort {
 
 constexpr int pow2ceil(int x) { int p = 1; while (p < x) p <<= 1; return p; }
 constexpr int ilog2(int x) { return x <= 1 ? 0 : 1 + ilog2(x >> 1); }
-constexpr int blocks(int n) { return (n + 1) / 2; }                                      // whole Philox blocks of n normals
-constexpr int slots(int n, int w) { return pow2ceil(2 * ((blocks(n) + w - 1) / w)); }    // M
-constexpr bool spread(int n, int w) { return w > 1 && slots(n, w) <= kSortUnrollMax; }
+// The layout for `per` normals to a Philox block, a power of two: 2 for doubles, 4 for binary32 values (team_sample_f32.hpp)
+constexpr int blocks(int n, int per = 2) { return (n + per - 1) / per; }                 // whole Philox blocks of n normals
+constexpr int slots(int n, int w, int per = 2) { return pow2ceil(per * ((blocks(n, per) + w - 1) / w)); }      // M
+constexpr bool spread(int n, int w, int per = 2) { return w > 1 && slots(n, w, per) <= kSortUnrollMax; }
 
 // where draw i lies before the sort, where rank i lies after it
-constexpr int draw_lane(int i, int w) { return (i >> 1) & (w - 1); }
-constexpr int draw_slot(int i, int w) { return 2 * ((i >> 1) / w) + (i & 1); }
-constexpr int draw_of(int lane, int slot, int w) { return 2 * (lane + w * (slot >> 1)) + (slot & 1); }
+constexpr int draw_lane(int i, int w, int per = 2) { return (i >> ilog2(per)) & (w - 1); }
+constexpr int draw_slot(int i, int w, int per = 2) { return per * ((i >> ilog2(per)) / w) + (i & (per - 1)); }
+constexpr int draw_of(int lane, int slot, int w, int per = 2) {
+  return per * (lane + w * (slot >> ilog2(per))) + (slot & (per - 1));
+}
 constexpr int rank_lane(int i, int m) { return i / m; }
 constexpr int rank_slot(int i, int m) { return i & (m - 1); }
 
@@ -106,77 +114,147 @@ SABC_SORT_HD void run_schedule(const int w, const int m, T *x) {
 }  // namespace sabc
 
 #if defined(__HIPCC__) || defined(__HIPCC_RTC__)
-// ---- the device's half: included from the end of device_rng.hpp, whose NormalStream, box_muller, team_pick and emit it uses ----
+// ---- the device's half: included from the end of device_rng.hpp, whose NormalStream, box_muller, team_pick and emit it uses
 namespace sabc {
 namespace teamsort {
 
-// v from lane ^ DIST of the row (device_models.hpp: xor_lane, restated where hipRTC sees it): DPP quad_perm for 1 and 2,
-// ds_swizzle in bit-mask mode for 4 and 8
-template <int DIST>
-__device__ __forceinline__ double xor_lane(const double v) {
-  static_assert(DIST == 1 || DIST == 2 || DIST == 4 || DIST == 8, "a lane of the own row of 16");
-  int lo = __double2loint(v), hi = __double2hiint(v);
-  if constexpr (DIST == 1) {
-    lo = __builtin_amdgcn_mov_dpp(lo, 0xB1, 0xF, 0xF, true);           // quad_perm [1,0,3,2]
-    hi = __builtin_amdgcn_mov_dpp(hi, 0xB1, 0xF, 0xF, true);
-  } else if constexpr (DIST == 2) {
-    lo = __builtin_amdgcn_mov_dpp(lo, 0x4E, 0xF, 0xF, true);           // quad_perm [2,3,0,1]
-    hi = __builtin_amdgcn_mov_dpp(hi, 0x4E, 0xF, 0xF, true);
-  } else {
-    constexpr int pattern = 0x1F | (DIST << 10);                        // and_mask 0x1f, or 0, xor DIST
-    lo = __builtin_amdgcn_ds_swizzle(lo, pattern);
-    hi = __builtin_amdgcn_ds_swizzle(hi, pattern);
-  }
-  return __hiloint2double(hi, lo);
-}
-__device__ __forceinline__ double vmin(double a, double b) { double r; asm("v_min_f64 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
-__device__ __forceinline__ double vmax(double a, double b) { double r; asm("v_max_f64 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
-__device__ __forceinline__ double vmin_neg(double a, double b) { double r; asm("v_min_f64 %0, %1, -%2" : "=v"(r) : "v"(a), "v"(b)); return r; }
+// What the element type of a sample decides -- all of it: the executor, the store and the summaries below are written once over
+// Element<T>.  Specialisations of one template, not overloads: a dependent call on a fundamental type gets no argument-dependent
+// lookup, so an overload declared behind the template that calls it (team_sample_f32.hpp's) would not be found.
+//   per_block: normals to a Philox block;  inf()
+//   Slots<N, W, M>: the spread store's members v[M] and sorted with its fill_normals, the base of SampleStore.  (Per type, in the
+//   text it had and called by the simulator itself: as one loop over the normals of a block the f64 form's i + 1 < N is no longer
+//   folded into a comparison of the lane with a constant, the two types transform and store in different orders, and behind one
+//   more call the same text is scheduled differently.)
+//   xor_lane<DIST>(v): v from lane ^ DIST of the row;  vmin, vmax, vmin_neg(a, b) = min(a, -b);  flip_sign(v, bit 31 or 0)
+//   select_slot(v, slot), pick<W>(v, lane): a slot and a lane known at run time
+//   the replicated store's fill_normals, order_statistic and quantile, as a simulator writes them by hand for this type
+template <class T>
+struct Element;
+template <int W>
+__device__ __forceinline__ int team_lane() { return (int)(threadIdx.x & (unsigned)(W - 1)); }      // q, the lane's place in the team
 
-template <int W, int M, int I>
-__device__ __forceinline__ void run_step_device(double (&v)[M], const int q) {
+template <>
+struct Element<double> {
+  static constexpr int per_block = 2;
+  static __device__ __forceinline__ double inf() { return sortnet::inf_(0.0); }
+  template <int N, int W, int M>
+  struct Slots {
+    double v[M];
+    bool sorted;
+    template <class F>
+    __device__ __forceinline__ void fill_normals(NormalStream &rng, F &&f) {
+      const int q = team_lane<W>();
+#pragma unroll
+      for (int a = 0; a < M / 2; ++a) {
+        if (a * W < blocks(N)) {                         // (a constant: some lane of the team has a block a)
+          double z0, z1;
+          box_muller(stream_block(rng.seed, rng.pid, rng.purpose, rng.iter, rng.k + (uint32_t)(a * W + q)), z0, z1);
+          const double x0 = f(z0), x1 = f(z1);
+          const int i = 2 * (a * W + q);
+          v[2 * a] = i < N ? sortnet::min_(x0, sortnet::inf_(0.0)) : sortnet::inf_(0.0);
+          v[2 * a + 1] = i + 1 < N ? sortnet::min_(x1, sortnet::inf_(0.0)) : sortnet::inf_(0.0);
+        } else {
+          v[2 * a] = v[2 * a + 1] = sortnet::inf_(0.0);
+        }
+      }
+      rng.k += (uint32_t)blocks(N);
+      sorted = false;
+    }
+  };
+
+  // (device_models.hpp: xor_lane, restated where hipRTC sees it) DPP quad_perm for 1 and 2, ds_swizzle in bit-mask mode for 4 and 8
+  template <int DIST>
+  static __device__ __forceinline__ double xor_lane(const double v) {
+    static_assert(DIST == 1 || DIST == 2 || DIST == 4 || DIST == 8, "a lane of the own row of 16");
+    int lo = __double2loint(v), hi = __double2hiint(v);
+    if constexpr (DIST == 1) {
+      lo = __builtin_amdgcn_mov_dpp(lo, 0xB1, 0xF, 0xF, true);           // quad_perm [1,0,3,2]
+      hi = __builtin_amdgcn_mov_dpp(hi, 0xB1, 0xF, 0xF, true);
+    } else if constexpr (DIST == 2) {
+      lo = __builtin_amdgcn_mov_dpp(lo, 0x4E, 0xF, 0xF, true);           // quad_perm [2,3,0,1]
+      hi = __builtin_amdgcn_mov_dpp(hi, 0x4E, 0xF, 0xF, true);
+    } else {
+      constexpr int pattern = 0x1F | (DIST << 10);                        // and_mask 0x1f, or 0, xor DIST
+      lo = __builtin_amdgcn_ds_swizzle(lo, pattern);
+      hi = __builtin_amdgcn_ds_swizzle(hi, pattern);
+    }
+    return __hiloint2double(hi, lo);
+  }
+  static __device__ __forceinline__ double vmin(double a, double b) { double r; asm("v_min_f64 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
+  static __device__ __forceinline__ double vmax(double a, double b) { double r; asm("v_max_f64 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
+  static __device__ __forceinline__ double vmin_neg(double a, double b) { double r; asm("v_min_f64 %0, %1, -%2" : "=v"(r) : "v"(a), "v"(b)); return r; }
+  static __device__ __forceinline__ double flip_sign(const double v, const int flip) { return __hiloint2double(__double2hiint(v) ^ flip, __double2loint(v)); }
+
+  // a select per slot, no indexed access (the array stays in registers).  Chosen by 32-bit halves, the two v_cndmask_b32 a select
+  // of doubles is anyway: a select between two LOADED doubles is turned into a load from a selected address while the array is
+  // still memory to the compiler, and that leaves it in scratch.
+  template <int M>
+  static __device__ __forceinline__ double select_slot(const double (&v)[M], const int slot) {
+    int lo = __double2loint(v[0]), hi = __double2hiint(v[0]);
+#pragma unroll
+    for (int r = 1; r < M; ++r) {
+      lo = slot == r ? __double2loint(v[r]) : lo;
+      hi = slot == r ? __double2hiint(v[r]) : hi;
+    }
+    return __hiloint2double(hi, lo);
+  }
+  template <int W>
+  static __device__ __forceinline__ double pick(const double v, const uint32_t lane) { return team_pick<W>(v, lane); }
+
+  template <int N, class F>
+  static __device__ __forceinline__ void fill_normals(NormalStream &rng, double (&x)[N], F &&f) {
+    int at_ = 0;
+    rng.for_pairs(N >> 1, [&](const double z0, const double z1) {
+      x[at_] = f(z0);
+      x[at_ + 1] = f(z1);
+      at_ += 2;
+    });
+    if (N & 1) {
+      double z0, z1;
+      rng.pair(z0, z1);
+      x[N - 1] = f(z0);
+    }
+  }
+  template <int N>
+  static __device__ __forceinline__ double order_statistic(const double (&x)[N], const int rank) {
+    return sabc::order_statistic(x, N, rank);
+  }
+  template <int N>
+  static __device__ __forceinline__ double quantile(const double (&x)[N], const double p) { return sabc::quantile(x, N, p); }
+};
+
+template <class T, int W, int M, int I>
+__device__ __forceinline__ void run_step_device(T (&v)[M], const int q) {
+  using E = Element<T>;
   constexpr Step s = step_at(W, M, I);
   constexpr int mask = sign_mask(s, W, M), before = I > 0 ? sign_mask(step_at(W, M, I > 0 ? I - 1 : 0), W, M) : 0;
   if constexpr (mask != before) {
     const int flip = (__builtin_popcount(q & (mask ^ before)) & 1) << 31;
 #pragma unroll
-    for (int r = 0; r < M; ++r) v[r] = __hiloint2double(__double2hiint(v[r]) ^ flip, __double2loint(v[r]));
+    for (int r = 0; r < M; ++r) v[r] = E::flip_sign(v[r], flip);
   }
   if constexpr (s.cross) {
-    double p[M];
+    T p[M];
 #pragma unroll
-    for (int r = 0; r < M; ++r) p[r] = xor_lane<s.dist>(v[r]);
+    for (int r = 0; r < M; ++r) p[r] = E::template xor_lane<s.dist>(v[r]);
 #pragma unroll
-    for (int r = 0; r < M; ++r) v[r] = vmin_neg(v[r], p[r]);
+    for (int r = 0; r < M; ++r) v[r] = E::vmin_neg(v[r], p[r]);
   } else {
     constexpr int desc = descending_slot_bit(s, M);
 #pragma unroll
     for (int r = 0; r < M; ++r) {
       if (r & s.dist) continue;
-      const double lo = vmin(v[r], v[r | s.dist]), hi = vmax(v[r], v[r | s.dist]);
+      const T lo = E::vmin(v[r], v[r | s.dist]), hi = E::vmax(v[r], v[r | s.dist]);
       v[r] = (r & desc) ? hi : lo;
       v[r | s.dist] = (r & desc) ? lo : hi;
     }
   }
 }
-template <int W, int M, int... I>
-__device__ __forceinline__ void run_schedule_device(double (&v)[M], const int q, sortnet::seq<I...>) {
-  (run_step_device<W, M, I>(v, q), ...);
+template <class T, int W, int M, int... I>
+__device__ __forceinline__ void run_schedule_device(T (&v)[M], const int q, sortnet::seq<I...>) {
+  (run_step_device<T, W, M, I>(v, q), ...);
   static_assert(sign_mask(step_at(W, M, step_count(W, M) - 1), W, M) == 0, "the last step leaves the values themselves");
-}
-
-// slot `slot` of v, the slot known at run time: a select per slot, no indexed access (the array stays in registers).
-// (Chosen by 32-bit halves, the two v_cndmask_b32 a select of doubles is anyway: a select between two LOADED doubles is turned
-// into a load from a selected address while the array is still memory to the compiler, and that leaves it in scratch.)
-template <int M>
-__device__ __forceinline__ double select_slot(const double (&v)[M], const int slot) {
-  int lo = __double2loint(v[0]), hi = __double2hiint(v[0]);
-#pragma unroll
-  for (int r = 1; r < M; ++r) {
-    lo = slot == r ? __double2loint(v[r]) : lo;
-    hi = slot == r ? __double2hiint(v[r]) : hi;
-  }
-  return __hiloint2double(hi, lo);
 }
 
 // the type-7 quantile of sort_network.hpp (sabc::quantile: the same arithmetic, the same handling of infinities) over a
@@ -194,83 +272,80 @@ __device__ __forceinline__ double quantile_at(At &&at, double p) {
   return d - d == 0.0 ? a + g * d : (1.0 - g) * a + g * b;
 }
 
-// ---- spread over the team ----
-template <int N, int W, bool SPREAD>
-struct SampleStore {
-  static constexpr int M = slots(N, W);
-  static_assert(W == 4 || W == 16, "a quad or a row of 16 lanes");
-  double v[M];
-  bool sorted;
-
-  static __device__ __forceinline__ int lane() { return (int)(threadIdx.x & (unsigned)(W - 1)); }
-  __device__ __forceinline__ int element(const int q, const int r) const { return sorted ? q * M + r : draw_of(q, r, W); }
-
-  template <class F>
-  __device__ __forceinline__ void fill_normals(NormalStream &rng, F &&f) {
-    const int q = lane();
-#pragma unroll
-    for (int a = 0; a < M / 2; ++a) {
-      if (a * W < blocks(N)) {                           // (a constant: some lane of the team has a block a)
-        double z0, z1;
-        box_muller(stream_block(rng.seed, rng.pid, rng.purpose, rng.iter, rng.k + (uint32_t)(a * W + q)), z0, z1);
-        const double x0 = f(z0), x1 = f(z1);
-        const int i = 2 * (a * W + q);
-        v[2 * a] = i < N ? sortnet::min_(x0, sortnet::inf_(0.0)) : sortnet::inf_(0.0);
-        v[2 * a + 1] = i + 1 < N ? sortnet::min_(x1, sortnet::inf_(0.0)) : sortnet::inf_(0.0);
-      } else {
-        v[2 * a] = v[2 * a + 1] = sortnet::inf_(0.0);
-      }
-    }
-    rng.k += (uint32_t)blocks(N);
-    sorted = false;
+// the team's butterflies over the lane distances 1, 2, 4, 8, in f64 whatever the element type: every lane ends with the same bits
+template <int W>
+__device__ __forceinline__ double team_add(double s) {
+  s = s + Element<double>::xor_lane<1>(s);
+  s = s + Element<double>::xor_lane<2>(s);
+  if constexpr (W == 16) {
+    s = s + Element<double>::xor_lane<4>(s);
+    s = s + Element<double>::xor_lane<8>(s);
   }
+  return s;
+}
+template <int W, bool MAX>
+__device__ __forceinline__ double team_extreme(double s) {
+  const auto pick = [](const double a, const double b) { return MAX ? sortnet::max_(a, b) : sortnet::min_(a, b); };
+  s = pick(s, Element<double>::xor_lane<1>(s));
+  s = pick(s, Element<double>::xor_lane<2>(s));
+  if constexpr (W == 16) {
+    s = pick(s, Element<double>::xor_lane<4>(s));
+    s = pick(s, Element<double>::xor_lane<8>(s));
+  }
+  return s;
+}
+// the extreme of g(i, x[i]) over an array a lane holds whole
+template <bool MAX, int N, class T, class G>
+__device__ __forceinline__ double array_extreme(const T (&x)[N], G &&g) {
+  double s = MAX ? -sortnet::inf_(0.0) : sortnet::inf_(0.0);
+  for (int i = 0; i < N; ++i) s = MAX ? sortnet::max_(s, (double)g(i, x[i])) : sortnet::min_(s, (double)g(i, x[i]));
+  return s;
+}
+
+// ---- spread over the team: T v[M] per lane, P = Element<T>::per_block normals to a block (v, sorted, fill_normals: Slots') ----
+template <class T, int N, int W, bool SPREAD>
+struct SampleStore : Element<T>::template Slots<N, W, slots(N, W, Element<T>::per_block)> {
+  using E = Element<T>;
+  static constexpr int P = E::per_block, M = slots(N, W, P);
+  static_assert(W == 4 || W == 16, "a quad or a row of 16 lanes");
+  static_assert(M >= P && M <= kSortUnrollMax, "whole blocks in a lane's registers");
+  using Slots = typename E::template Slots<N, W, M>;
+  using Slots::v;
+  using Slots::sorted;
+
+  static __device__ __forceinline__ int lane() { return team_lane<W>(); }
+  __device__ __forceinline__ int element(const int q, const int r) const { return sorted ? q * M + r : draw_of(q, r, W, P); }
+
   template <class G>
   __device__ __forceinline__ void fill(G &&g) {
     const int q = lane();
 #pragma unroll
     for (int r = 0; r < M; ++r) {
-      const int i = draw_of(q, r, W);
-      v[r] = sortnet::inf_(0.0);
-      if (i < N) v[r] = sortnet::min_(g(i), sortnet::inf_(0.0));
+      const int i = draw_of(q, r, W, P);
+      v[r] = E::inf();
+      if (i < N) {
+        const T x = g(i);
+        v[r] = sortnet::min_(x, E::inf());
+      }
     }
     sorted = false;
   }
   __device__ __forceinline__ void sort() {
-    run_schedule_device<W, M>(v, lane(), typename sortnet::make_seq<step_count(W, M)>::type{});
+    run_schedule_device<T, W, M>(v, lane(), typename sortnet::make_seq<step_count(W, M)>::type{});
     sorted = true;
   }
-  __device__ __forceinline__ double drawn(const int i) const {
-    return team_pick<W>(select_slot<M>(v, draw_slot(i, W)), (uint32_t)draw_lane(i, W));
+  __device__ __forceinline__ T drawn(const int i) const {
+    return E::template pick<W>(E::template select_slot<M>(v, draw_slot(i, W, P)), (uint32_t)draw_lane(i, W, P));
   }
-  __device__ __forceinline__ double at(const int i) const {
-    return team_pick<W>(select_slot<M>(v, rank_slot(i, M)), (uint32_t)rank_lane(i, M));
+  __device__ __forceinline__ T at(const int i) const {
+    return E::template pick<W>(E::template select_slot<M>(v, rank_slot(i, M)), (uint32_t)rank_lane(i, M));
   }
-  __device__ __forceinline__ double order_statistic(const int rank) const {
-    const double x = at(rank >= 1 && rank <= N ? rank - 1 : 0);        // (uniform over the team: every lane takes part)
-    return rank >= 1 && rank <= N ? x : sortnet::inf_(0.0);
+  __device__ __forceinline__ T order_statistic(const int rank) const {
+    const T x = at(rank >= 1 && rank <= N ? rank - 1 : 0);             // (uniform over the team: every lane takes part)
+    return rank >= 1 && rank <= N ? x : E::inf();
   }
   __device__ __forceinline__ double quantile(const double p) const {
-    return quantile_at<N>([&](const int i) { return at(i); }, p);
-  }
-  static __device__ __forceinline__ double team_add(double s) {
-    s = s + xor_lane<1>(s);
-    s = s + xor_lane<2>(s);
-    if constexpr (W == 16) {
-      s = s + xor_lane<4>(s);
-      s = s + xor_lane<8>(s);
-    }
-    return s;
-  }
-  template <bool MAX>
-  static __device__ __forceinline__ double team_extreme(double s) {
-    const auto pick = [](const double a, const double b) { return MAX ? sortnet::max_(a, b) : sortnet::min_(a, b); };
-    s = pick(s, xor_lane<1>(s));
-    s = pick(s, xor_lane<2>(s));
-    if constexpr (W == 16) {
-      s = pick(s, xor_lane<4>(s));
-      s = pick(s, xor_lane<8>(s));
-    }
-    return s;
+    return quantile_at<N>([&](const int i) { return (double)at(i); }, p);
   }
   template <class G>
   __device__ __forceinline__ double sum(G &&g) const {
@@ -281,7 +356,7 @@ struct SampleStore {
       const int i = element(q, r);
       t[r] = i < N ? g(i, v[r]) : 0.0;
     }
-    return reduce::finish_sum(team_add(reduce::lane_tree(t)));
+    return reduce::finish_sum(team_add<W>(reduce::lane_tree(t)));
   }
   template <bool MAX, class G>
   __device__ __forceinline__ double extreme(G &&g) const {
@@ -290,9 +365,9 @@ struct SampleStore {
 #pragma unroll
     for (int r = 0; r < M; ++r) {
       const int i = element(q, r);
-      if (i < N) s = MAX ? sortnet::max_(s, g(i, v[r])) : sortnet::min_(s, g(i, v[r]));
+      if (i < N) s = MAX ? sortnet::max_(s, (double)g(i, v[r])) : sortnet::min_(s, (double)g(i, v[r]));
     }
-    return team_extreme<MAX>(s);
+    return team_extreme<W, MAX>(s);
   }
   __device__ __forceinline__ void emit(NormalStream &rng, const long long first_output) const {
     if (!emitting(rng)) return;
@@ -300,53 +375,80 @@ struct SampleStore {
 #pragma unroll
     for (int r = 0; r < M; ++r) {
       const int i = element(q, r);
-      if (i < N) sabc::emit(rng, first_output + i, v[r]);
+      if (i < N) sabc::emit(rng, first_output + i, (double)v[r]);
     }
   }
 };
 
 // ---- replicated: a lane per particle, or a sample too long for the team's registers ----
-template <int N, int W>
-struct SampleStore<N, W, false> {
+template <class T, int N, int W>
+struct SampleStore<T, N, W, false> {
+  using E = Element<T>;
   static_assert(W == 1 || W == 4 || W == 16, "a lane, a quad or a row of 16 lanes");
-  double x[N];
+  T x[N];
 
   template <class F>
-  __device__ __forceinline__ void fill_normals(NormalStream &rng, F &&f) {
-    int at_ = 0;
-    rng.for_pairs(N >> 1, [&](const double z0, const double z1) {
-      x[at_] = f(z0);
-      x[at_ + 1] = f(z1);
-      at_ += 2;
-    });
-    if (N & 1) {
-      double z0, z1;
-      rng.pair(z0, z1);
-      x[N - 1] = f(z0);
-    }
-  }
+  __device__ __forceinline__ void fill_normals(NormalStream &rng, F &&f) { E::fill_normals(rng, x, f); }
   template <class G>
   __device__ __forceinline__ void fill(G &&g) {
     for (int i = 0; i < N; ++i) x[i] = g(i);
   }
   __device__ __forceinline__ void sort() { sort_ascending(x); }          // (a NaN enters as +inf there)
-  __device__ __forceinline__ double drawn(const int i) const { return x[i]; }
-  __device__ __forceinline__ double at(const int i) const { return x[i]; }
-  __device__ __forceinline__ double order_statistic(const int rank) const { return sabc::order_statistic(x, N, rank); }
-  __device__ __forceinline__ double quantile(const double p) const { return sabc::quantile(x, N, p); }
+  __device__ __forceinline__ T drawn(const int i) const { return x[i]; }
+  __device__ __forceinline__ T at(const int i) const { return x[i]; }
+  __device__ __forceinline__ T order_statistic(const int rank) const { return E::order_statistic(x, rank); }
+  __device__ __forceinline__ double quantile(const double p) const { return E::quantile(x, p); }
   template <class G>
   __device__ __forceinline__ double sum(G &&g) const {
-    return reduce::tree_sum_of(N, [&](const int i) { return g(i, x[i]); });
+    return reduce::tree_sum_of(N, [&](const int i) { return (double)g(i, x[i]); });
   }
   template <bool MAX, class G>
-  __device__ __forceinline__ double extreme(G &&g) const {
-    double s = MAX ? -sortnet::inf_(0.0) : sortnet::inf_(0.0);
-    for (int i = 0; i < N; ++i) s = MAX ? sortnet::max_(s, g(i, x[i])) : sortnet::min_(s, g(i, x[i]));
-    return s;
-  }
+  __device__ __forceinline__ double extreme(G &&g) const { return array_extreme<MAX>(x, g); }
   __device__ __forceinline__ void emit(NormalStream &rng, const long long first_output) const {
     if (!emitting(rng) || (threadIdx.x & (unsigned)(W - 1)) != 0) return;
-    for (int i = 0; i < N; ++i) sabc::emit(rng, first_output + i, x[i]);
+    for (int i = 0; i < N; ++i) sabc::emit(rng, first_output + i, (double)x[i]);
+  }
+};
+
+// max(g), min(g), sum(), mean() and moments(mean, var) of a container C of N elements that has sum(g) and extreme<MAX>(g)
+// (Sample, SampleF32, Series): an element widens to double on its way in
+template <class C, int N>
+struct Summaries {
+  __device__ __forceinline__ const C &self() const { return static_cast<const C &>(*this); }
+  template <class G> __device__ __forceinline__ double max(G &&g) const { return self().template extreme<true>(g); }
+  template <class G> __device__ __forceinline__ double min(G &&g) const { return self().template extreme<false>(g); }
+  __device__ __forceinline__ double sum() const { return self().sum([](const int, const auto x) { return (double)x; }); }
+  __device__ __forceinline__ double mean() const { return sum() / (double)N; }
+  __device__ __forceinline__ void moments(double &mean_out, double &var_out) const {
+    const double m = mean();
+    mean_out = m;
+    var_out = N > 1 ? self().sum([&](const int, const auto x) { return ((double)x - m) * ((double)x - m); }) / (double)(N > 1 ? N - 1 : 1)
+                    : 0.0;
+  }
+};
+
+// sabc::Sample and sabc::SampleF32: the store, the summaries and the distances to observed data (doubles, as every data segment)
+template <class T, int N, int W>
+struct SampleOf : SampleStore<T, N, W, spread(N, W, Element<T>::per_block)>, Summaries<SampleOf<T, N, W>, N> {
+  static_assert(N >= 1, "a sample holds at least one value");
+  static constexpr int size = N, lanes = W;
+  static constexpr bool spread = teamsort::spread(N, W, Element<T>::per_block);
+  using Store = SampleStore<T, N, W, spread>;
+  using Store::sum;
+  using Summaries<SampleOf, N>::sum;
+
+  __device__ __forceinline__ double wasserstein1(const int seg = 0) const {
+    return Store::sum([&](const int i, const T x) { return __builtin_fabs((double)x - data_at(i, seg)); }) / (double)N;
+  }
+  __device__ __forceinline__ double wasserstein2_squared(const int seg = 0) const {
+    return Store::sum([&](const int i, const T x) { const double d = (double)x - data_at(i, seg); return d * d; }) / (double)N;
+  }
+  __device__ __forceinline__ double ks(const int seg = 0) const {
+    const long long m = data_len(seg);
+    const double top = Store::template extreme<true>([&](const int i, const T x) {
+      return reduce::ks_term(i, N, m, count_less((double)x, seg), count_less_equal((double)x, seg));
+    });
+    return top / ((double)N * (double)m);
   }
 };
 
@@ -366,36 +468,7 @@ struct SampleStore<N, W, false> {
 // lane reads its own M consecutive observations), ks(seg) the Kolmogorov-Smirnov distance for any data_len(seg) >= 1
 // (N data_len(seg) < 2^53).
 template <int N, int W>
-struct Sample : teamsort::SampleStore<N, W, teamsort::spread(N, W)> {
-  static_assert(N >= 1, "a sample holds at least one value");
-  static constexpr int size = N, lanes = W;
-  static constexpr bool spread = teamsort::spread(N, W);
-  using Store = teamsort::SampleStore<N, W, teamsort::spread(N, W)>;
-  using Store::sum;
-
-  template <class G> __device__ __forceinline__ double max(G &&g) const { return Store::template extreme<true>(g); }
-  template <class G> __device__ __forceinline__ double min(G &&g) const { return Store::template extreme<false>(g); }
-  __device__ __forceinline__ double sum() const { return Store::sum([](const int, const double x) { return x; }); }
-  __device__ __forceinline__ double mean() const { return sum() / (double)N; }
-  __device__ __forceinline__ void moments(double &mean_out, double &var_out) const {
-    const double m = mean();
-    mean_out = m;
-    var_out = N > 1 ? Store::sum([&](const int, const double x) { return (x - m) * (x - m); }) / (double)(N > 1 ? N - 1 : 1) : 0.0;
-  }
-  __device__ __forceinline__ double wasserstein1(const int seg = 0) const {
-    return Store::sum([&](const int i, const double x) { return __builtin_fabs(x - data_at(i, seg)); }) / (double)N;
-  }
-  __device__ __forceinline__ double wasserstein2_squared(const int seg = 0) const {
-    return Store::sum([&](const int i, const double x) { const double d = x - data_at(i, seg); return d * d; }) / (double)N;
-  }
-  __device__ __forceinline__ double ks(const int seg = 0) const {
-    const long long m = data_len(seg);
-    const double top = Store::template extreme<true>([&](const int i, const double x) {
-      return reduce::ks_term(i, N, m, count_less(x, seg), count_less_equal(x, seg));
-    });
-    return top / ((double)N * (double)m);
-  }
-};
+using Sample = teamsort::SampleOf<double, N, W>;
 
 }  // namespace sabc
 #endif

@@ -106,8 +106,8 @@ SABC_SORT_HD double run_lagged_sum(const int w, const int m, const int n, const 
 }  // namespace sabc
 
 #if defined(__HIPCC__) || defined(__HIPCC_RTC__)
-// ---- the device's half: included from the end of device_rng.hpp, behind team_sample.hpp whose select_slot, xor_lane and team_add
-// it uses ----
+// ---- the device's half: included from the end of device_rng.hpp, behind team_sample.hpp whose Element<double>::select_slot,
+// team_add, team_extreme, array_extreme and Summaries it uses ----
 namespace sabc {
 namespace series {
 
@@ -125,7 +125,6 @@ template <int N, int W, bool SPREAD>
 struct SeriesStore {
   static constexpr int M = teamsort::slots(N, W);
   static_assert(W == 4 || W == 16, "a quad or a row of 16 lanes");
-  using Sums = teamsort::SampleStore<N, W, true>;      // team_add, team_extreme: the butterflies of Sample
   double v[M];
 
   static __device__ __forceinline__ int lane() { return (int)(threadIdx.x & (unsigned)(W - 1)); }
@@ -170,7 +169,7 @@ struct SeriesStore {
       if (time_of(q, r, M) < N) v[r] = g(time_of(q, r, M), v[r], other.v[r]);
   }
   __device__ __forceinline__ double at(const int t) const {
-    return team_pick<W>(teamsort::select_slot<M>(v, time_slot(t, M)), (uint32_t)time_lane(t, M));
+    return team_pick<W>(teamsort::Element<double>::select_slot<M>(v, time_slot(t, M)), (uint32_t)time_lane(t, M));
   }
   __device__ __forceinline__ void emit(NormalStream &rng, const long long first_output, const int first) const {
     if (!emitting(rng)) return;
@@ -227,7 +226,7 @@ struct SeriesStore {
         term[r] = t < N && t >= first + L ? g(t, v[r], back.v[r]) : 0.0;
       }
     }
-    return reduce::finish_sum(Sums::team_add(reduce::lane_tree(term)));
+    return reduce::finish_sum(teamsort::team_add<W>(reduce::lane_tree(term)));
   }
   template <bool MAX, class G>
   __device__ __forceinline__ double extreme(G &&g) const {
@@ -238,7 +237,7 @@ struct SeriesStore {
       const int t = time_of(q, r, M);
       if (t < N) s = MAX ? sortnet::max_(s, g(t, v[r])) : sortnet::min_(s, g(t, v[r]));
     }
-    return Sums::template team_extreme<MAX>(s);
+    return teamsort::team_extreme<W, MAX>(s);
   }
 };
 
@@ -288,11 +287,7 @@ struct SeriesStore<N, W, false> {
     return reduce::tree_sum_of(N, [&](const int t) { return t >= first + L ? g(t, x[t], x[t >= L ? t - L : 0]) : 0.0; });
   }
   template <bool MAX, class G>
-  __device__ __forceinline__ double extreme(G &&g) const {
-    double s = MAX ? -sortnet::inf_(0.0) : sortnet::inf_(0.0);
-    for (int t = 0; t < N; ++t) s = MAX ? sortnet::max_(s, g(t, x[t])) : sortnet::min_(s, g(t, x[t]));
-    return s;
-  }
+  __device__ __forceinline__ double extreme(G &&g) const { return teamsort::array_extreme<MAX>(x, g); }
 };
 
 }  // namespace series
@@ -310,7 +305,7 @@ struct SeriesStore<N, W, false> {
 //   sum(g), max(g), min(g) over g(t, x_t); sum(), mean(); moments(mean, var): Sample's definitions over the time index.
 // Values pass through unchanged: no NaN policy.  The same bits for every W.
 template <int N, int W>
-struct Series : series::SeriesStore<N, W, teamsort::spread(N, W)> {
+struct Series : series::SeriesStore<N, W, teamsort::spread(N, W)>, teamsort::Summaries<Series<N, W>, N> {
   static_assert(N >= 1, "a series holds at least one value");
   static constexpr int size = N, lanes = W;
   static constexpr bool spread = teamsort::spread(N, W);
@@ -341,15 +336,7 @@ struct Series : series::SeriesStore<N, W, teamsort::spread(N, W)> {
   template <class G> __device__ __forceinline__ double sum(G &&g) const {
     return Store::template lagged_sum_store<0>([&](const int t, const double a, const double) { return g(t, a); }, 0);
   }
-  template <class G> __device__ __forceinline__ double max(G &&g) const { return Store::template extreme<true>(g); }
-  template <class G> __device__ __forceinline__ double min(G &&g) const { return Store::template extreme<false>(g); }
-  __device__ __forceinline__ double sum() const { return sum([](const int, const double x) { return x; }); }
-  __device__ __forceinline__ double mean() const { return sum() / (double)N; }
-  __device__ __forceinline__ void moments(double &mean_out, double &var_out) const {
-    const double m = mean();
-    mean_out = m;
-    var_out = N > 1 ? sum([&](const int, const double x) { return (x - m) * (x - m); }) / (double)(N > 1 ? N - 1 : 1) : 0.0;
-  }
+  using teamsort::Summaries<Series, N>::sum;           // sum(), and with it max(g), min(g), mean(), moments(mean, var)
 };
 
 }  // namespace sabc

@@ -1,7 +1,8 @@
 // The CPU proof of csrc/team_sample_f32.hpp, built from the headers alone (tests/test_team_sample_f32_host.py: g++, address and
 // undefined-behaviour sanitizers where their runtimes exist).  For teams of W = 4 and 16 lanes:
-//   * THE LAYOUT: for every N <= 132, draw -> (draw_lane_f32, draw_slot_f32) is injective, lands below M on the lane that generates
-//     the draw's block of four, its image plus the pad slots is all W M positions, and draw_of_f32 inverts it;
+//   * THE LAYOUT (teamsort's with four normals to a block): for every N <= 132, draw -> (draw_lane, draw_slot) is injective, lands
+//     below M on the lane that generates the draw's block of four, its image plus the pad slots is all W M positions, and draw_of
+//     inverts it;
 //   * the spread / replicated boundary: N = 32 W is spread, N = 32 W + 1 is replicated, W = 1 always is;
 //   * the FLOAT SIGNED-VALUE EXECUTOR in plain C++ -- what the device does on float v[M]: sign flips by teamsort::sign_mask on the
 //     word's top bit, a cross-lane step as min(own, -partner's), an in-lane step one min and one max ascending on the stored
@@ -12,182 +13,47 @@
 //   * THE f64 TREE over the widened floats -- every lane adds reduce::lane_tree of its M terms on the sorted layout, the team
 //     follows with the butterfly over lane distances 1, 2, 4, 8 -- equals reduce::tree_sum_of bit for bit for every N <= 64 and
 //     for 100 and 128, and every lane ends with the same bits.
-// Prints one line per failure and a summary; the exit status is 1 if anything failed.
+// The executor's model and the checks on it are ../team_sample/signed_executor.hpp's, shared with the f64 proof; the layout for every
+// N and the widened tree are here.  Prints one line per failure and a summary; the exit status is 1 if anything failed.
 #include "team_sample_f32.hpp"
 
-#include <algorithm>
-#include <cmath>
-#include <cstdint>
-#include <cstdio>
-#include <cstring>
-#include <limits>
-#include <vector>
+#include "../team_sample/signed_executor.hpp"
 
 namespace {
 
-namespace ts = sabc::teamsort;
 namespace rd = sabc::reduce;
-int g_failures = 0, g_checks = 0;
-const float kInf = std::numeric_limits<float>::infinity();
 
-void fail(const char *what, int w, int n) {
-  if (++g_failures <= 20) std::printf("FAIL %s W=%d N=%d\n", what, w, n);
-}
-
-uint64_t g_state = 0x9E3779B97F4A7C15ull;              // splitmix64, fixed seed
-uint64_t next_u64() {
-  uint64_t z = (g_state += 0x9E3779B97F4A7C15ull);
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
-
-static_assert(ts::slots_f32(128, 16) == 8 && ts::slots_f32(128, 4) == 32 && ts::slots_f32(45, 16) == 4 && ts::slots_f32(45, 4) == 16, "slots per lane");
-static_assert(ts::slots_f32(1, 16) == 4 && ts::slots_f32(64, 16) == 4 && ts::slots_f32(65, 16) == 8 && ts::slots_f32(17, 4) == 8, "whole blocks of four");
-static_assert(ts::spread_f32(128, 4) && !ts::spread_f32(129, 4) && ts::spread_f32(512, 16) && !ts::spread_f32(513, 16) && !ts::spread_f32(8, 1),
+static_assert(ts::slots(128, 16, 4) == 8 && ts::slots(128, 4, 4) == 32 && ts::slots(45, 16, 4) == 4 && ts::slots(45, 4, 4) == 16, "slots per lane");
+static_assert(ts::slots(1, 16, 4) == 4 && ts::slots(64, 16, 4) == 4 && ts::slots(65, 16, 4) == 8 && ts::slots(17, 4, 4) == 8, "whole blocks of four");
+static_assert(ts::spread(128, 4, 4) && !ts::spread(129, 4, 4) && ts::spread(512, 16, 4) && !ts::spread(513, 16, 4) && !ts::spread(8, 1, 4),
               "spread while a lane's slots fit the unrolled size");
-static_assert(ts::blocks_f32(1) == 1 && ts::blocks_f32(4) == 1 && ts::blocks_f32(5) == 2 && ts::blocks_f32(128) == 32, "whole blocks");
-
-bool same_bits(float a, float b) { return std::memcmp(&a, &b, sizeof(float)) == 0; }
-bool same_bits(double a, double b) { return std::memcmp(&a, &b, sizeof(double)) == 0; }
-float flip_sign(float x) {                             // v_xor_b32 with 0x80000000
-  uint32_t u;
-  std::memcpy(&u, &x, 4);
-  u ^= 0x80000000u;
-  std::memcpy(&x, &u, 4);
-  return x;
-}
-
-constexpr int kMaxPositions = 16 * sabc::kSortUnrollMax;
-
-// the device's executor in plain C++: y[q m + r] holds x or -x as sign_mask says
-void run_signed(const int w, const int m, float *y) {
-  float t[kMaxPositions];
-  int before = 0;
-  for (int i = 0; i < ts::step_count(w, m); ++i) {
-    const ts::Step s = ts::step_at(w, m, i);
-    const int mask = ts::sign_mask(s, w, m);
-    if (mask != before)
-      for (int q = 0; q < w; ++q)
-        if (__builtin_popcount(q & (mask ^ before)) & 1)
-          for (int r = 0; r < m; ++r) y[q * m + r] = flip_sign(y[q * m + r]);
-    before = mask;
-    if (s.cross) {
-      for (int p = 0; p < w * m; ++p) t[p] = y[p];
-      for (int q = 0; q < w; ++q)
-        for (int r = 0; r < m; ++r) y[q * m + r] = std::fmin(t[q * m + r], -t[(q ^ s.dist) * m + r]);
-    } else {
-      const int desc = ts::descending_slot_bit(s, m);
-      for (int q = 0; q < w; ++q)
-        for (int r = 0; r < m; ++r) {
-          if (r & s.dist) continue;
-          const float lo = std::fmin(y[q * m + r], y[q * m + (r | s.dist)]), hi = std::fmax(y[q * m + r], y[q * m + (r | s.dist)]);
-          y[q * m + r] = (r & desc) ? hi : lo;
-          y[q * m + (r | s.dist)] = (r & desc) ? lo : hi;
-        }
-    }
-  }
-  if (before != 0) fail("the last step's sign mask is not 0", w, m);
-}
+static_assert(ts::blocks(1, 4) == 1 && ts::blocks(4, 4) == 1 && ts::blocks(5, 4) == 2 && ts::blocks(128, 4) == 32, "whole blocks");
 
 void layout(const int w, const int n) {
   ++g_checks;
-  const int m = ts::slots_f32(n, w);
+  const int m = ts::slots(n, w, 4);
   if (m < 4 || (m & (m - 1)) || w * m < n) { fail("slots per lane", w, n); return; }
   std::vector<int> owner((size_t)(w * m), -1);
   for (int i = 0; i < n; ++i) {
-    const int q = ts::draw_lane_f32(i, w), r = ts::draw_slot_f32(i, w);
+    const int q = ts::draw_lane(i, w, 4), r = ts::draw_slot(i, w, 4);
     if (q < 0 || q >= w || r < 0 || r >= m) { fail("a draw outside the team's slots", w, n); return; }
     if (q != (i / 4) % w || (r & 3) != (i & 3)) fail("a draw away from the lane that generates its block", w, n);
     if (owner[(size_t)(q * m + r)] != -1) { fail("two draws in one slot", w, n); return; }
     owner[(size_t)(q * m + r)] = i;
-    if (ts::draw_of_f32(q, r, w) != i) fail("draw_of_f32 does not invert the layout", w, n);
+    if (ts::draw_of(q, r, w, 4) != i) fail("draw_of does not invert the layout", w, n);
   }
   int pads = 0;
   for (int q = 0; q < w; ++q)
     for (int r = 0; r < m; ++r) {
-      const int i = ts::draw_of_f32(q, r, w);
+      const int i = ts::draw_of(q, r, w, 4);
       if (owner[(size_t)(q * m + r)] == -1) {
         ++pads;
         if (i < n) fail("a pad slot whose draw index is below N", w, n);
       } else if (owner[(size_t)(q * m + r)] != i) {
-        fail("draw_of_f32 disagrees with the layout", w, n);
+        fail("draw_of disagrees with the layout", w, n);
       }
     }
   if (pads + n != w * m) fail("draws plus pad slots are not all positions", w, n);
-}
-
-// SampleF32<n, w> as the header lays it out: fill in draw order, sort, read in rank order
-std::vector<float> team_sort(const int w, const std::vector<float> &in, bool *signed_agrees = nullptr) {
-  const int n = (int)in.size();
-  std::vector<float> out(in);
-  if (!ts::spread_f32(n, w)) {                         // replicated: the array every lane holds, sabc::sort_ascending
-    sabc::sort_ascending(out.data(), n);
-    return out;
-  }
-  const int m = ts::slots_f32(n, w), positions = w * m;
-  float x[kMaxPositions], y[kMaxPositions];
-  for (int p = 0; p < positions; ++p) x[p] = kInf;
-  for (int i = 0; i < n; ++i) x[ts::draw_lane_f32(i, w) * m + ts::draw_slot_f32(i, w)] = std::fmin(in[(size_t)i], kInf);      // NaN -> +inf
-  for (int p = 0; p < positions; ++p) y[p] = x[p];
-  ts::run_schedule(w, m, x);
-  run_signed(w, m, y);
-  bool agree = true;
-  for (int p = 0; p < positions; ++p) agree = agree && (same_bits(x[p], y[p]) || (x[p] == 0.0f && y[p] == 0.0f));
-  if (signed_agrees) *signed_agrees = agree;
-  for (int i = 0; i < n; ++i) out[(size_t)i] = y[ts::rank_lane(i, m) * m + ts::rank_slot(i, m)];
-  for (int p = n; p < positions; ++p)
-    if (y[p] != kInf) fail("a pad slot among the first N ranks", w, n);
-  return out;
-}
-
-void zero_one(const int w, const int n) {
-  std::vector<float> in((size_t)n);
-  for (uint32_t bits = 0; bits < (1u << n); ++bits) {
-    int ones = 0;
-    for (int i = 0; i < n; ++i) { in[(size_t)i] = (float)((bits >> i) & 1u); ones += (int)((bits >> i) & 1u); }
-    bool agree = true;
-    const std::vector<float> out = team_sort(w, in, &agree);
-    bool ok = agree;
-    for (int i = 0; i < n; ++i) ok = ok && out[(size_t)i] == (float)(i >= n - ones ? 1 : 0);
-    ++g_checks;
-    if (!ok) { fail(agree ? "0-1 input" : "0-1 input: the signed executor differs from the schedule", w, n); return; }
-  }
-}
-
-void against_std_sort(const int w, const int n) {
-  for (int kind = 0; kind < 4; ++kind) {
-    std::vector<float> in((size_t)n);
-    for (int i = 0; i < n; ++i) {
-      const uint64_t u = next_u64();
-      switch (kind) {
-        case 0: in[(size_t)i] = (float)(int32_t)(u >> 40) * 0x1p-12f - 2048.0f; break;             // random
-        case 1: in[(size_t)i] = (float)(u % 7) - 3.0f; break;                                       // many duplicates
-        case 2: in[(size_t)i] = u % 5 == 0 ? kInf : u % 5 == 1 ? -kInf : (float)(u % 1000); break;   // infinities
-        default: in[(size_t)i] = (float)(n - i); break;                                            // reversed
-      }
-    }
-    std::vector<float> want(in);
-    std::sort(want.begin(), want.end());
-    bool agree = true;
-    const std::vector<float> out = team_sort(w, in, &agree);
-    ++g_checks;
-    if (!agree) fail("the signed executor differs from the schedule", w, n);
-    if (!std::equal(want.begin(), want.end(), out.begin())) fail("against std::sort", w, n);
-  }
-}
-
-void nan_policy(const int w, const int n) {
-  std::vector<float> in((size_t)n);
-  for (int i = 0; i < n; ++i) in[(size_t)i] = (float)((i * 7) % n);
-  in[(size_t)(n / 2)] = std::numeric_limits<float>::quiet_NaN();
-  in[0] = std::numeric_limits<float>::quiet_NaN();
-  const std::vector<float> out = team_sort(w, in);
-  ++g_checks;
-  bool ok = out[(size_t)(n - 1)] == kInf && out[(size_t)(n - 2)] == kInf;
-  for (int i = 0; i + 1 < n; ++i) ok = ok && out[(size_t)i] <= out[(size_t)(i + 1)];
-  for (int i = 0; i < n - 2; ++i) ok = ok && out[(size_t)i] < kInf;
-  if (!ok) fail("NaN enters as +inf", w, n);
 }
 
 template <int M>
@@ -206,10 +72,10 @@ double lane_tree_m(const int m, const double *pos) {
   return std::nan("");
 }
 
-// SampleStoreF32::sum after sort(): position q m + r holds rank q m + r widened to double, a pad slot adds +0.0
+// SampleF32's sum after sort(): position q m + r holds rank q m + r widened to double, a pad slot adds +0.0
 void widened_tree(const int w, const int n) {
-  if (!ts::spread_f32(n, w)) return;
-  const int m = ts::slots_f32(n, w);
+  if (!ts::spread(n, w, 4)) return;
+  const int m = ts::slots(n, w, 4);
   for (int kind = 0; kind < 3; ++kind) {
     std::vector<float> x((size_t)n);
     for (int i = 0; i < n; ++i) {
@@ -237,10 +103,10 @@ int main() {
   for (const int w : {4, 16}) {
     for (int n = 1; n <= 132; ++n) layout(w, n);
     ++g_checks;
-    if (!ts::spread_f32(32 * w, w) || ts::spread_f32(32 * w + 1, w) || ts::spread_f32(32 * w, 1)) fail("the spread / replicated boundary", w, 32 * w);
-    for (int n = 1; n <= 16; ++n) zero_one(w, n);
-    for (const int n : {45, 100, 128, 512}) against_std_sort(w, n);
-    for (const int n : {3, 8, 17, 45, 128}) nan_policy(w, n);
+    if (!ts::spread(32 * w, w, 4) || ts::spread(32 * w + 1, w, 4) || ts::spread(32 * w, 1, 4)) fail("the spread / replicated boundary", w, 32 * w);
+    for (int n = 1; n <= 16; ++n) zero_one<float>(w, n);
+    for (const int n : {45, 100, 128, 512}) against_std_sort<float>(w, n);
+    for (const int n : {3, 8, 17, 45, 128}) nan_policy<float>(w, n);
     for (int n = 1; n <= 64; ++n) widened_tree(w, n);
     for (const int n : {100, 128}) widened_tree(w, n);
   }
