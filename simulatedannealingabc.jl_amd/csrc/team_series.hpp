@@ -28,8 +28,19 @@
 //
 // A series is not sorted, so there is no NaN policy: values pass through unchanged.
 //
-// Out of scope: prefix scans (cumsum, AR recurrences), whose rounding depends on the order of association and so on W; a
-// binary32 twin; lags between two series other than through lag<L>() followed by zip.
+//   recur / recur_with / cumsum: a state carried from t = 0 upwards, one application of f per time step -- THE SEQUENTIAL LOOP,
+//   whose bits are those of the plain `for` over x[t] for every W by construction: no order of association is chosen.  A team
+//   runs it as a RELAY over the ceil(N / M) lanes that hold a time < N, in lane order.  In phase p every lane of the team starts
+//   from the same carried state and runs its own M slots in order through f, with its own times and its own elements; lane p
+//   alone keeps the outputs (a select behind the computation, no branch around it), and its state is handed to every lane with
+//   team_pick_ct<W, p> per component: the carry of phase p + 1 and, behind the last phase, the value returned.  The pick is
+//   issued by every lane in uniform control flow, and nothing uninitialised is read: the other lanes compute f on the true carry
+//   and their own real elements and discard the result.  So every lane issues N evaluations of f, as a lane alone does -- the
+//   recurrence is not divided; the draws, maps, zips, summaries and registers around it are.  series::run_recur is the schedule
+//   on plain arrays.
+//
+// Out of scope: a parallel scan for associative operations (its rounding would depend on the order of association, other bits
+// than the loop's); a binary32 twin; lags between two series other than through lag<L>() followed by zip.
 //
 // The layout, the lag schedule and the block ownership are constexpr and compile with a plain C++ compiler, as
 // teamsort::step_at does; tests/team_series/check_series.cpp runs them on plain arrays of W M positions.
@@ -100,6 +111,70 @@ SABC_SORT_HD double run_lagged_sum(const int w, const int m, const int n, const 
   if (l > 0) run_lag(w, m, n, l, 0.0, x, lagged);
   for (int p = 0; p < w * m; ++p) term[p] = p < n && p >= first + l ? g(p, x[p], l > 0 ? lagged[p] : x[p]) : 0.0;
   return run_team_sum(w, m, term, sums);
+}
+
+
+// ---- recurrences ----
+// the state of a recurrence with K components, 1 <= K <= 4 (a plain double is the other State)
+template <int K>
+struct Carry {
+  static_assert(K >= 1 && K <= 4, "a Carry holds 1 to 4 doubles");
+  double v[K];
+};
+template <class State>
+struct CarryOf {
+  static_assert(sizeof(State) == 0, "the State of a recurrence is double or sabc::series::Carry<K>, 1 <= K <= 4");
+};
+template <>
+struct CarryOf<double> {
+  static constexpr int size = 1;
+  static SABC_SORT_HD double &at(double &s, int) { return s; }
+};
+template <int K>
+struct CarryOf<Carry<K>> {
+  static constexpr int size = K;
+  static SABC_SORT_HD double &at(Carry<K> &s, const int k) { return s.v[k]; }
+};
+// the lanes of the relay: those that hold a time < n
+constexpr int relay_lanes(int n, int m) { return (n + m - 1) / m; }
+
+// One lane's share of one phase: from the carried state s through its own m slots in order, out[r] = f(t, s, x[r]) and s advanced
+// where first <= t < n, x[r] and s as they were elsewhere.  f is evaluated at every slot and chosen behind the evaluation.
+template <class State, class F>
+SABC_SORT_HD void recur_lane(const int q, const int m, const int n, const int first, State &s, F &&f, const double *x, double *out) {
+  for (int r = 0; r < m; ++r) {
+    const int t = time_of(q, r, m);
+    const bool live = first <= t && t < n;
+    State next = s;
+    const double o = f(t, next, x[r]);
+    for (int k = 0; k < CarryOf<State>::size; ++k) CarryOf<State>::at(s, k) = live ? CarryOf<State>::at(next, k) : CarryOf<State>::at(s, k);
+    out[r] = live ? o : x[r];
+  }
+}
+// recur(s0, f, first) on plain arrays of w m positions, x -> out (they may be the same array), phase by phase as the device
+// walks them, the evaluations of the lanes that discard theirs included: `discarded(p, q, out_of_lane_q, state_of_lane_q)` sees
+// what lane q != p computed in phase p before the select (the CPU proof overwrites it and finds nothing changed).
+template <class State, class F, class D>
+SABC_SORT_HD State run_recur(const int w, const int m, const int n, const int first, State s, F &&f, const double *x, double *out,
+                             D &&discarded) {
+  for (int p = 0; p < w * m; ++p) out[p] = x[p];
+  for (int p = 0; p < relay_lanes(n, m); ++p) {
+    State handed = s;
+    for (int q = 0; q < w; ++q) {
+      State mine = s;
+      double kept[kSortUnrollMax];
+      recur_lane(q, m, n, first, mine, f, out + q * m, kept);
+      if (q != p) discarded(p, q, kept, mine);
+      for (int r = 0; r < m; ++r) out[q * m + r] = q == p ? kept[r] : out[q * m + r];
+      if (q == p) handed = mine;                       // team_pick_ct<W, p>
+    }
+    s = handed;
+  }
+  return s;
+}
+template <class State, class F>
+SABC_SORT_HD State run_recur(const int w, const int m, const int n, const int first, State s, F &&f, const double *x, double *out) {
+  return run_recur(w, m, n, first, s, f, x, out, [](int, int, double *, State &) {});
 }
 
 }  // namespace series
@@ -239,6 +314,48 @@ struct SeriesStore {
     }
     return teamsort::team_extreme<W, MAX>(s);
   }
+
+  // the relay: phase P.  Every lane from the same carry through its own slots; lane P keeps the outputs; its state to all.
+  template <int P, class State, class F>
+  __device__ __forceinline__ void recur_phase(State &s, F &&f, const int first, const int q) {
+    State mine = s;
+    double kept[M];
+#pragma unroll
+    for (int r = 0; r < M; ++r) {
+      const int t = time_of(q, r, M);
+      const bool live = first <= t && t < N;
+      State next = mine;
+      const double o = f(t, next, r);
+#pragma unroll
+      for (int k = 0; k < CarryOf<State>::size; ++k)
+        CarryOf<State>::at(mine, k) = live ? CarryOf<State>::at(next, k) : CarryOf<State>::at(mine, k);
+      kept[r] = live ? o : v[r];
+    }
+#pragma unroll
+    for (int r = 0; r < M; ++r) v[r] = q == P ? kept[r] : v[r];
+    // by every lane of the team, in uniform control flow: a DPP move reads 0 from a lane that is switched off
+#pragma unroll
+    for (int k = 0; k < CarryOf<State>::size; ++k) CarryOf<State>::at(s, k) = team_pick_ct<W, P>(CarryOf<State>::at(mine, k));
+  }
+  template <class State, class F, int... P>
+  __device__ __forceinline__ void recur_phases(State &s, F &&f, const int first, sortnet::seq<P...>) {
+    const int q = lane();
+    (recur_phase<P>(s, f, first, q), ...);
+  }
+  // f(t, State &s, slot r): the members below bind the slot to this series' element (and another's)
+  template <class State, class F>
+  __device__ __forceinline__ State recur_store(State s, F &&f, const int first) {
+    recur_phases(s, f, first, typename sortnet::make_seq<relay_lanes(N, M)>::type{});
+    return s;
+  }
+  template <class State, class F>
+  __device__ __forceinline__ State recur_one(State s, F &&f, const int first) {
+    return recur_store(s, [&](const int t, State &c, const int r) { return f(t, c, v[r]); }, first);
+  }
+  template <class State, class F>
+  __device__ __forceinline__ State recur_two(const SeriesStore &other, State s, F &&f, const int first) {
+    return recur_store(s, [&](const int t, State &c, const int r) { return f(t, c, v[r], other.v[r]); }, first);
+  }
 };
 
 // ---- replicated: a lane per particle, or a series too long for the team's registers ----
@@ -288,6 +405,17 @@ struct SeriesStore<N, W, false> {
   }
   template <bool MAX, class G>
   __device__ __forceinline__ double extreme(G &&g) const { return teamsort::array_extreme<MAX>(x, g); }
+  // the plain loop
+  template <class State, class F>
+  __device__ __forceinline__ State recur_one(State s, F &&f, const int first) {
+    for (int t = first > 0 ? first : 0; t < N; ++t) x[t] = f(t, s, x[t]);
+    return s;
+  }
+  template <class State, class F>
+  __device__ __forceinline__ State recur_two(const SeriesStore &other, State s, F &&f, const int first) {
+    for (int t = first > 0 ? first : 0; t < N; ++t) x[t] = f(t, s, x[t], other.x[t]);
+    return s;
+  }
 };
 
 }  // namespace series
@@ -303,6 +431,16 @@ struct SeriesStore<N, W, false> {
 //   autocovariance<L>(center = 0.0, first = 0), 0 <= L < N: that sum of (x_t - c)(x_{t-L} - c), each product rounded on its own
 //   (series::rounded_product), divided by N - first.
 //   sum(g), max(g), min(g) over g(t, x_t); sum(), mean(); moments(mean, var): Sample's definitions over the time index.
+//   recur(s0, f, first = 0): for t = first .. N-1 in time order x_t <- f(t, s, x_t), where f takes `State &s` and may change it;
+//   returns the state behind t = N-1, the same value on every lane.  recur_with(other, s0, f, first = 0): the same with
+//   f(t, s, x_t, other_t).  cumsum(): recur(0.0, s = s + x).  State is double or sabc::series::Carry<K> (double v[K], 1 <= K <= 4).
+//   Elements t < first are left as they are and do not touch the state.  The bits are the sequential loop's for every W.
+//   THE CONTRACT ON f: a pure function of its arguments.  The library may evaluate it on lanes that discard the result (the relay
+//   at the head of this file), so f has no side effects: it does not call emit, does not draw from rng and does not use the
+//   state as an index into memory.
+//   ROUNDING IS THE CALLER'S: the run-time compiler is told -ffp-contract=fast, so an a * b + c inside f may fuse on the device
+//   and not in a transcription.  f writes fma(...) where it wants one and series::rounded_product where it wants a product
+//   rounded on its own.  cumsum only adds.
 // Values pass through unchanged: no NaN policy.  The same bits for every W.
 template <int N, int W>
 struct Series : series::SeriesStore<N, W, teamsort::spread(N, W)>, teamsort::Summaries<Series<N, W>, N> {
@@ -337,6 +475,20 @@ struct Series : series::SeriesStore<N, W, teamsort::spread(N, W)>, teamsort::Sum
     return Store::template lagged_sum_store<0>([&](const int t, const double a, const double) { return g(t, a); }, 0);
   }
   using teamsort::Summaries<Series, N>::sum;           // sum(), and with it max(g), min(g), mean(), moments(mean, var)
+
+  template <class State, class F>
+  __device__ __forceinline__ State recur(const State s0, F &&f, const int first = 0) {
+    static_assert(series::CarryOf<State>::size >= 1, "double or Carry<K>");
+    return Store::recur_one(s0, f, first);
+  }
+  template <class State, class F>
+  __device__ __forceinline__ State recur_with(const Series &other, const State s0, F &&f, const int first = 0) {
+    static_assert(series::CarryOf<State>::size >= 1, "double or Carry<K>");
+    return Store::recur_two(other, s0, f, first);
+  }
+  __device__ __forceinline__ void cumsum() {
+    recur(0.0, [](const int, double &s, const double x) { s = s + x; return s; });
+  }
 };
 
 }  // namespace sabc

@@ -20,7 +20,7 @@ import Dates
 import Base: show
 
 export sabc, update_population!, RandomWalk, DifferentialEvolution, StretchMove,
-       DeviceDistance, GaussianIID, Gaussian2D, GandK, LotkaVolterra, DeviceSource, StochasticSIR, LotkaVolterraF32, NormalMoments, StochasticSIRSeries, GandKQuantiles, GandKSample, GandKSampleF32, MA2, SourcePrior,
+       DeviceDistance, GaussianIID, Gaussian2D, GandK, LotkaVolterra, DeviceSource, StochasticSIR, LotkaVolterraF32, NormalMoments, StochasticSIRSeries, GandKQuantiles, GandKSample, GandKSampleF32, MA2, GARCH11, SourcePrior,
        comm_unique_id, simulate_outputs, posterior_predictive
 
 const libsabc = get(ENV, "SABC_HIP_LIB", joinpath(@__DIR__, "..", "libsabc_hip.so"))
@@ -388,6 +388,42 @@ end
 # τ_0 .. τ_n_lags as the device computes them: rounded products, the tree over the innovations' n + 2 times (two leading zeros)
 ma2_autocovariances(y, n_lags) =
     Float64[tree_sum(vcat(zeros(2 + j), y[(j + 1):end] .* y[1:(end - j)])) / length(y) for j in 0:n_lags]
+"""
+    GARCH11(; summaries_obs=nothing, n_obs=100, n_lags=2, sigma2_0=1.0, team_lanes=nothing)
+    GARCH11(y_obs; n_lags=2, team_lanes=nothing)
+
+GARCH(1,1): θ = (ω, α, β), y_t = σ_t z_t and σ²_{t+1} = ω + α y_t² + β σ²_t for `n_obs` times from σ²_0 = `sigma2_0` (a positive
+number; the second method sets it to the mean of y_obs²).  Summaries of r_t = y_t²: the mean and the autocovariances about it at
+lags 0 .. `n_lags` (at most 7), ρ_0 = |mean(r) − obs[0]|, ρ_{1+j} = |acov_j(r) − obs[1+j]|.  One data segment, `summaries_obs`, of
+`n_lags + 2` finite values; the second method takes it from an observed series of returns (`garch11_summaries`: the device's own
+sums).  A `DeviceSource` of device_sources/garch11.hip on `sabc::Series::recur` (csrc/team_series.hpp): one recurrence in time
+order over the normals.  `team_lanes` = 1, 4 or 16: that many lanes per particle, the state relayed from lane to lane, the same
+bits as the default (`nothing`: a private array per lane).
+"""
+function GARCH11(; summaries_obs=nothing, n_obs::Integer=100, n_lags::Integer=2, sigma2_0::Real=1.0, team_lanes=nothing)
+    0 <= n_lags <= 7 || throw(ArgumentError("n_lags must be in 0..7"))
+    n_lags < n_obs <= 1024 || throw(ArgumentError("n_obs must be above n_lags and at most 1024"))
+    (isfinite(sigma2_0) && sigma2_0 > 0) || throw(ArgumentError("sigma2_0 must be a positive finite number"))
+    text = read(joinpath(@__DIR__, "..", "device_sources", "garch11.hip"), String)
+    head = "#define GARCH11_N_OBS $(n_obs)\n#define GARCH11_N_LAGS $(n_lags)\n" * (team_lanes === nothing ? "" : "#define GARCH11_TEAM 1\n")
+    DeviceSource(head * text, 3, Int(n_lags) + 2; params=Float64[n_obs, n_lags, sigma2_0],
+                 data=summaries_obs === nothing ? nothing : (summaries_obs,), data_names=(:summaries_obs,),
+                 validate=segs -> check_garch11_data(segs, Int(n_lags)), team_lanes=team_lanes)
+end
+function GARCH11(y_obs; n_lags::Integer=2, team_lanes=nothing)
+    obs = garch11_summaries(data_segment(y_obs), n_lags)
+    GARCH11(; summaries_obs=obs, n_obs=length(y_obs), n_lags=n_lags, sigma2_0=obs[1], team_lanes=team_lanes)
+end
+# the source reads summaries_obs[j] and writes ρ[j] for every j < n_lags + 2
+check_garch11_data(segs, n_lags) = (length(segs) == 1 && length(segs[1]) == n_lags + 2 && all(isfinite, segs[1])) ||
+    throw(ArgumentError("summaries_obs is one segment of $(n_lags + 2) finite values"))
+# mean(r), acov_0(r) .. acov_n_lags(r) of r = y² as the device computes them: rounded products, the tree over the n times
+function garch11_summaries(y, n_lags)
+    r = y .* y
+    c = tree_sum(r) / length(r)
+    d = r .- c
+    vcat(c, Float64[tree_sum(vcat(zeros(j), d[(j + 1):end] .* d[1:(end - j)])) / length(r) for j in 0:n_lags])
+end
 """
     SourcePrior(d)
 

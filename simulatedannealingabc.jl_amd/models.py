@@ -249,8 +249,14 @@ class DeviceSource(DeviceDistance):
     is the canonical sum of g(t, x_t, x_{t-L}) over t >= first + L, `x.autocovariance<L>(center = 0.0, first = 0)` that sum of
     (x_t - c)(x_{t-L} - c), each product rounded on its own, over N - first; `sum`, `max`, `min`, `mean`, `moments` as for a
     `Sample`, over the time index.  Position equals index for every width, so all of them give the same bits for 1, 4 and 16
-    lanes, always.  Values pass through unchanged (no NaN policy: nothing is sorted).  Not there: prefix scans (cumsum, AR
-    recurrences), a binary32 twin.  `MA2` is the shipped model on it."""
+    lanes, always.  Values pass through unchanged (no NaN policy: nothing is sorted).  `MA2` is the shipped model on these.
+    Recurrences run in time order: `x.recur(s0, f, first = 0)` is the sequential loop x_t <- f(t, s, x_t) for t = first .. N-1 with
+    `State &s` carried from step to step (State: double or `sabc::series::Carry<K>`, K <= 4 doubles) and returns the last state;
+    `x.recur_with(other, s0, f, first = 0)` passes other_t as well; `x.cumsum()`.  A team relays the state from lane to lane, so
+    the bits are the plain loop's for every width.  f must be a pure function of its arguments -- no emit, no draw from rng, no
+    memory indexed by the state: the team evaluates it on lanes that discard the result -- and the rounding inside f is the
+    caller's (write `fma` and `sabc::series::rounded_product`; a bare a * b + c may fuse).  `GARCH11` is the shipped model on it.
+    Not there: a parallel scan for associative operations, a binary32 twin."""
     model_id = _lib.MODEL_USER
 
     def __init__(self, hip_source: str, n_para: int, n_stats: int, params=(), data=None, data_names=None, n_outputs=None,
@@ -681,3 +687,76 @@ class MA2(DeviceSource):
             raise ValueError(f"acov_obs is one segment of n_lags + 1 = {self.n_lags + 1} values (the autocovariances at lags 0 .. {self.n_lags})")
         if not np.all(np.isfinite(segments[0])):
             raise ValueError("acov_obs must be finite")
+
+
+class GARCH11(DeviceSource):
+    """GARCH(1,1) (Bollerslev 1986), the model shipped on `sabc::Series::recur`: theta = (omega, alpha, beta), y_t = sigma_t z_t and
+    sigma^2_{t+1} = omega + alpha y_t^2 + beta sigma^2_t for t = 0 .. n_obs-1, with z the next n_obs normals of the particle's
+    stream and sigma^2_0 = `sigma2_0`, a positive number (`from_observations` sets it to the mean of y_obs^2).  Summaries of the
+    squared returns r_t = y_t^2: their mean and their autocovariances about it at lags 0 .. n_lags (n_lags <= 7), rho_0 =
+    |mean(r) - obs_0|, rho_{1+j} = |acov_j(r) - obs_{1+j}|: n_stats = n_lags + 2.  `summaries_obs` is ONE data segment of
+    n_lags + 2 finite values -- another series' summaries are another `SabcHandle.set_data` or
+    `sabc(model, prior, summaries_obs=...)`, never another compilation --; `n_obs` and `n_lags` are compile-time constants of the
+    source, `sigma2_0` is one of its params.  `from_observations(y_obs)` computes `summaries_obs` from a series of returns with
+    the device's own sums (`summaries`), `observe(theta)` lets the device source simulate one.
+    Source: device_sources/garch11.hip on `sabc::Series<n_obs, W>` (csrc/team_series.hpp): one `recur` over the normals with the
+    state sigma^2_t -- two products rounded on their own, two explicit fmas --, then `mean` and `autocovariance<j>`.
+    `team_lanes` = 1, 4 or 16: the series spread over that many lanes per particle, the recurrence relayed from lane to lane in
+    time order; None (the default): the same text with a private array per lane.  All forms give the same bits, those of the
+    sequential loop.  Outputs: the returns y_t = copysign(sqrt(r_t), z_t) (`posterior_predictive` gives [n, n_rep, n_obs])."""
+    MAX_LAGS = 7
+    MAX_OBS = 1024                   # the series is 8 n_obs bytes of private memory per lane where it is not spread (twice: z and r)
+
+    def __init__(self, summaries_obs=None, n_obs=100, n_lags=2, sigma2_0=1.0, team_lanes=None, data_names=("summaries_obs",)):
+        if isinstance(n_lags, bool) or int(n_lags) != n_lags or not 0 <= int(n_lags) <= self.MAX_LAGS:
+            raise ValueError(f"n_lags must be an integer in 0..{self.MAX_LAGS}, got {n_lags!r}")
+        if isinstance(n_obs, bool) or int(n_obs) != n_obs or not int(n_lags) < int(n_obs) <= self.MAX_OBS:
+            raise ValueError(f"n_obs must be an integer above n_lags = {n_lags} and at most {self.MAX_OBS}, got {n_obs!r}")
+        if isinstance(sigma2_0, (bool, str)) or not (np.isfinite(float(sigma2_0)) and float(sigma2_0) > 0.0):
+            raise ValueError(f"sigma2_0 must be a positive finite number, got {sigma2_0!r}")
+        self.n_obs, self.n_lags, self.sigma2_0 = int(n_obs), int(n_lags), float(sigma2_0)
+        head = f"#define GARCH11_N_OBS {self.n_obs}\n#define GARCH11_N_LAGS {self.n_lags}\n" + ("" if team_lanes is None else "#define GARCH11_TEAM 1\n")
+        super().__init__(head + device_source_text("garch11"), 3, self.n_lags + 2, [self.n_obs, self.n_lags, self.sigma2_0],
+                         data=None if summaries_obs is None else [_segment(summaries_obs)], data_names=data_names,
+                         n_outputs=self.n_obs, team_lanes=team_lanes)
+
+    @staticmethod
+    def summaries(y, n_lags=2):
+        """mean(r), acov_0(r) .. acov_n_lags(r) of r = y^2 for a series of returns y (along the last axis) as the device computes
+        them: the canonical sum over the n_obs times, every product rounded on its own, the autocovariances about the mean and
+        divided by n_obs."""
+        y = np.asarray(y, dtype=np.float64)
+        r = y * y
+        n = r.shape[-1]
+        mean = _tree_sum(r) / float(n)
+        d = r - mean[..., None]
+        out = [mean]
+        for j in range(int(n_lags) + 1):
+            terms = np.zeros(r.shape)
+            terms[..., j:] = d[..., j:] * d[..., :n - j]
+            out.append(_tree_sum(terms) / float(n))
+        return np.stack(out, axis=-1)
+
+    @classmethod
+    def from_observations(cls, y_obs, n_lags=2, team_lanes=None):
+        """The model for an observed series of returns `y_obs`: n_obs = len(y_obs), summaries_obs = `summaries(y_obs, n_lags)`,
+        sigma2_0 = the mean of y_obs^2 (summaries_obs[0])."""
+        y_obs = _segment(y_obs)
+        obs = cls.summaries(y_obs, n_lags)
+        return cls(obs, n_obs=len(y_obs), n_lags=n_lags, sigma2_0=float(obs[0]), team_lanes=team_lanes)
+
+    @classmethod
+    def observe(cls, theta, n_obs=100, seed=None, sigma2_0=1.0, device=None):
+        """A series of n_obs returns made by the device source itself: one forward run at theta = (omega, alpha, beta) on the
+        predictive stream of particle 0, iteration 0 of `seed`."""
+        from .api import simulate_outputs
+        model = cls(np.zeros(2), n_obs=n_obs, n_lags=0, sigma2_0=sigma2_0)
+        return simulate_outputs(model, np.asarray(theta, dtype=np.float64).reshape(1, 3), seed=seed, device=device)[0, 0]
+
+    def validate_data(self, segments):
+        # the source reads summaries_obs[j] and writes rho[j] for every j < n_lags + 2
+        if len(segments) != 1 or len(segments[0]) != self.n_lags + 2:
+            raise ValueError(f"summaries_obs is one segment of n_lags + 2 = {self.n_lags + 2} values (the mean of the squared returns and "
+                             f"their autocovariances at lags 0 .. {self.n_lags})")
+        if not np.all(np.isfinite(segments[0])):
+            raise ValueError("summaries_obs must be finite")
