@@ -406,15 +406,6 @@ __device__ __forceinline__ double team_pick_ct(const double v) {
   const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), ctrl, 0xF, 0xF, true);
   return __hiloint2double(hi, lo);
 }
-// ... with the lane chosen at run time (uniform over the team): a branch per bit of j
-template <int W, int J0 = 0, int N = W>
-__device__ __forceinline__ double team_pick(const double v, const uint32_t j) {
-  if constexpr (N == 1) {
-    return team_pick_ct<W, J0>(v);
-  } else {
-    return (j & (uint32_t)(N / 2)) ? team_pick<W, J0 + N / 2, N / 2>(v, j) : team_pick<W, J0, N / 2>(v, j);
-  }
-}
 
 // ---- f32 draws: four N(0,1) per Philox block (NormalStream::quad_f32 / for_quads_f32) -------------------------------------
 // A block w = (x, y, z, w) gives (z0, z1) from (x, y) and (z2, z3) from (z, w).  Of a pair (a, b):
@@ -572,7 +563,7 @@ __device__ __forceinline__ void uniform_quad(const u32x4 w, float &u0, float &u1
 
 }  // namespace f32
 
-// team_pick_ct / team_pick for a binary32 value: one DPP move
+// team_pick_ct for a binary32 value: one DPP move
 template <int W, int J>
 __device__ __forceinline__ float team_pick_ct_f32(const float v) {
   static_assert((W == 4 || W == 16) && J >= 0 && J < W, "a quad or a row of 16 lanes");
@@ -583,14 +574,37 @@ __device__ __forceinline__ float team_pick_ct_f32(const float v) {
   asm("" : "+v"(r));
   return __int_as_float(r);
 }
-template <int W, int J0 = 0, int N = W>
-__device__ __forceinline__ float team_pick_f32(const float v, const uint32_t j) {
+
+// What the element type of a draw decides, for the code a team shares (NormalStream's team loops and fetch, below): how many
+// draws a Philox block gives, how its words become normals or uniforms, and the DPP move of one value.
+template <class T> struct TeamDraws;
+template <> struct TeamDraws<double> {
+  static constexpr int kPerBlock = 2;
+  static __device__ __forceinline__ void normals(const u32x4 w, double (&g)[2]) { box_muller(w, g[0], g[1]); }
+  static __device__ __forceinline__ void uniforms(const u32x4 w, double (&g)[2]) { g[0] = u52(w.x, w.y); g[1] = u52(w.z, w.w); }
+  template <int W, int J> static __device__ __forceinline__ double pick_ct(const double v) { return team_pick_ct<W, J>(v); }
+};
+template <> struct TeamDraws<float> {
+  static constexpr int kPerBlock = 4;
+  static __device__ __forceinline__ void normals(const u32x4 w, float (&g)[4]) { f32::box_muller_quad(w, g[0], g[1], g[2], g[3]); }
+  static __device__ __forceinline__ void uniforms(const u32x4 w, float (&g)[4]) { f32::uniform_quad(w, g[0], g[1], g[2], g[3]); }
+  template <int W, int J> static __device__ __forceinline__ float pick_ct(const float v) { return team_pick_ct_f32<W, J>(v); }
+};
+// the value lane (team base + j) holds, the lane chosen at run time (uniform over the team): a branch per bit of j
+template <int W, int J0 = 0, int N = W, class T>
+__device__ __forceinline__ T team_pick(const T v, const uint32_t j) {
   if constexpr (N == 1) {
-    return team_pick_ct_f32<W, J0>(v);
+    return TeamDraws<T>::template pick_ct<W, J0>(v);
   } else {
-    return (j & (uint32_t)(N / 2)) ? team_pick_f32<W, J0 + N / 2, N / 2>(v, j) : team_pick_f32<W, J0, N / 2>(v, j);
+    return (j & (uint32_t)(N / 2)) ? team_pick<W, J0 + N / 2, N / 2>(v, j) : team_pick<W, J0, N / 2>(v, j);
   }
 }
+// coop: the group of W blocks this lane holds one block of, for the single calls (NormalStream::fetch)
+template <class T> struct TeamBuf {
+  int block;                     // first block of the group (-1: none) ...
+  bool uniform;                  // ... held as uniforms or as normals
+  T v[TeamDraws<T>::kPerBlock];
+};
 
 // simulated pairs per loop trip of NormalStream::for_pairs with a lane per particle: independent Philox / Box-Muller chains for
 // the scheduler (k_update<1,1,1,0>: 92 -> 62 VGPRs, 246 -> ~240 us at n = 1e6); the draws are still handed out in stream order
@@ -621,6 +635,10 @@ template <int... J> struct make_lane_seq<0, J...> { using type = lane_seq<J...>;
 // SIMD its latency, not its issue, is what the team would wait for), handed out through DPP broadcasts whose lane is a
 // compile-time constant; the rest -- fewer than 4 W pairs -- in one more group of as many blocks per lane as it takes.  pair() / uniform_pair() / next() keep working in either mode, one
 // group of W at a time, the lane picked by branches on the stream position.
+//
+// The binary32 draws (quad_f32 / uniform_quad_f32 / for_quads_f32) share a stream the same way, a block being four floats where
+// it was two doubles: the team loop (for_team, tail, hand_out), fetch and its buffer are written once over the element type, and
+// TeamDraws<T> above holds what the type decides.
 struct NormalStream {
   uint64_t seed, pid, iter;
   uint32_t purpose, k;
@@ -628,38 +646,35 @@ struct NormalStream {
   bool have;
   int coop;                      // 0: every lane its own stream | 4, 16: the lanes of a team share one (see above)
                                  // | kCoopPlainLoop: as 0, with for_pairs as the plain loop over pair()
-  int buf_block;                 // coop: first block of the group of W this lane holds one block of (-1: none) ...
-  bool buf_uniform;              // ... as uniforms (uniform_pair) or as a Box-Muller pair
-  double b0, b1;
-  int fbuf_block;                // the same for the binary32 draws (quad_f32 / uniform_quad_f32), a buffer of their own
-  bool fbuf_uniform;
-  float fb0, fb1, fb2, fb3;
+  TeamBuf<double> buf64;         // coop: the group behind pair / uniform_pair ...
+  TeamBuf<float> buf32;          // ... and the one behind quad_f32 / uniform_quad_f32, a buffer of their own
   // where sabc::emit puts the outputs of THIS simulation: output i at out[i * out_stride], i < out_n.  Null from every
   // constructor: only the forward run (Sim<SABC_MODEL_USER>::run_out) sets a destination, so in every other kernel
   // the null is a constant after inlining and what a simulator does for its outputs is dead code there
   double *out;
   long long out_stride, out_n;
   __device__ __forceinline__ NormalStream(uint64_t seed_, uint64_t pid_, uint32_t purpose_, uint64_t iter_, int coop_ = 0)
-      : seed(seed_), pid(pid_), iter(iter_), purpose(purpose_), k(0), spare(0.0), have(false), coop(coop_), buf_block(-1),
-        buf_uniform(false), b0(0.0), b1(0.0), fbuf_block(-1),
-        fbuf_uniform(false), fb0(0.f), fb1(0.f), fb2(0.f), fb3(0.f), out(nullptr), out_stride(0), out_n(0) {}
+      : seed(seed_), pid(pid_), iter(iter_), purpose(purpose_), k(0), spare(0.0), have(false), coop(coop_),
+        buf64{-1, false, {}}, buf32{-1, false, {}}, out(nullptr), out_stride(0), out_n(0) {}
   __device__ __forceinline__ void set_outputs(double *out_, long long stride_, long long n_) {
     out = out_;
     out_stride = stride_;
     out_n = out_ ? n_ : 0;
   }
   __device__ __forceinline__ void pair(double &z0, double &z1) {  // consumes one whole block
-    if (coop == 4) { fetch<4>(k++, false, z0, z1); return; }
-    if (coop == 16) { fetch<16>(k++, false, z0, z1); return; }
-    box_muller(stream_block(seed, pid, purpose, iter, k++), z0, z1);
+    double g[2];
+    if (coop == 4) fetch<4>(k++, false, buf64, g);
+    else if (coop == 16) fetch<16>(k++, false, buf64, g);
+    else TeamDraws<double>::normals(stream_block(seed, pid, purpose, iter, k++), g);
+    z0 = g[0]; z1 = g[1];
   }
   // two U(0,1) draws from one whole block (the 52-bit uniforms the Box-Muller pair would have been made of)
   __device__ __forceinline__ void uniform_pair(double &u0, double &u1) {
-    if (coop == 4) { fetch<4>(k++, true, u0, u1); return; }
-    if (coop == 16) { fetch<16>(k++, true, u0, u1); return; }
-    const u32x4 w = stream_block(seed, pid, purpose, iter, k++);
-    u0 = u52(w.x, w.y);
-    u1 = u52(w.z, w.w);
+    double g[2];
+    if (coop == 4) fetch<4>(k++, true, buf64, g);
+    else if (coop == 16) fetch<16>(k++, true, buf64, g);
+    else TeamDraws<double>::uniforms(stream_block(seed, pid, purpose, iter, k++), g);
+    u0 = g[0]; u1 = g[1];
   }
   template <class F>
   __device__ __forceinline__ void for_pairs(const int n, F &&f) {
@@ -670,21 +685,25 @@ struct NormalStream {
   // mix freely with pair(), uniform_pair(), while_events and the count draws.  |z| <= 6.7637.
   // four N(0,1) from one block: (z0, z1) from its words (x, y), (z2, z3) from (z, w)
   __device__ __forceinline__ void quad_f32(float &z0, float &z1, float &z2, float &z3) {
-    if (coop == 4) { fetch_f32<4>(k++, false, z0, z1, z2, z3); return; }
-    if (coop == 16) { fetch_f32<16>(k++, false, z0, z1, z2, z3); return; }
-    f32::box_muller_quad(stream_block(seed, pid, purpose, iter, k++), z0, z1, z2, z3);
+    float g[4];
+    if (coop == 4) fetch<4>(k++, false, buf32, g);
+    else if (coop == 16) fetch<16>(k++, false, buf32, g);
+    else TeamDraws<float>::normals(stream_block(seed, pid, purpose, iter, k++), g);
+    z0 = g[0]; z1 = g[1]; z2 = g[2]; z3 = g[3];
   }
   // four U(0,1) from one block: u_i = ((w_i >> 9) + 1/2) 2^-23, exact, in (0, 1)
   __device__ __forceinline__ void uniform_quad_f32(float &u0, float &u1, float &u2, float &u3) {
-    if (coop == 4) { fetch_f32<4>(k++, true, u0, u1, u2, u3); return; }
-    if (coop == 16) { fetch_f32<16>(k++, true, u0, u1, u2, u3); return; }
-    f32::uniform_quad(stream_block(seed, pid, purpose, iter, k++), u0, u1, u2, u3);
+    float g[4];
+    if (coop == 4) fetch<4>(k++, true, buf32, g);
+    else if (coop == 16) fetch<16>(k++, true, buf32, g);
+    else TeamDraws<float>::uniforms(stream_block(seed, pid, purpose, iter, k++), g);
+    u0 = g[0]; u1 = g[1]; u2 = g[2]; u3 = g[3];
   }
   // f(z0, z1, z2, z3) for the next n blocks of the stream, in stream order: the loop to draw the bulk of binary32 normals with
   template <class F>
   __device__ __forceinline__ void for_quads_f32(const int n, F &&f) {
-    if (coop == 4) { for_quads_team<4>(n, f); return; }
-    if (coop == 16) { for_quads_team<16>(n, f); return; }
+    if (coop == 4) { for_team<float, 4>(n, f); return; }
+    if (coop == 16) { for_team<float, 16>(n, f); return; }
     if (coop == 0) {                                     // a lane per particle: the re-spelled block generator (namespace loop)
       f32::tables_f32_fill();                            // ... and the tables in binary32, converted once per call
 #pragma unroll kSimUnroll
@@ -832,28 +851,6 @@ struct NormalStream {
     }
     return count;
   }
-  // the events of one group, lane J's after lane J - 1's, while f says go on and the bound allows
-  template <int W, class F, int... J>
-  __device__ __forceinline__ bool hand_out_events(const double ge, const double gu, const int max_events, int &count, F &f, lane_seq<J...>) {
-    bool go = true;
-    ((go = go && count < max_events && (++count, f(team_pick_ct<W, J>(ge), team_pick_ct<W, J>(gu)))), ...);
-    return go;
-  }
-  // a team per particle: blocks k + count + q on lane q, one block per lane per group
-  template <int W, class F>
-  __device__ __forceinline__ int while_events_team(const int max_events, F &f) {
-    using lanes = typename make_lane_seq<W>::type;
-    const uint32_t q = threadIdx.x & (uint32_t)(W - 1);
-    int count = 0;
-    bool go = true;
-    while (go && count < max_events) {
-      const u32x4 w = stream_block(seed, pid, purpose, iter, k + (uint32_t)count + q);
-      const double ge = 0.5 * neg2_log_tab(u52(w.x, w.y)), gu = u52(w.z, w.w);
-      go = hand_out_events<W>(ge, gu, max_events, count, f, lanes{});
-    }
-    k += (uint32_t)count;
-    return count;
-  }
   // a lane per particle, the re-spelled loop (namespace loop)
   template <class F>
   __device__ __forceinline__ void for_pairs_lane(const int n, F &f) {
@@ -868,8 +865,8 @@ struct NormalStream {
   // a team per particle, or a lane per particle with the plain loop over pair() (kCoopPlainLoop)
   template <class F>
   __device__ __forceinline__ void for_pairs_plain(const int n, F &&f) {
-    if (coop == 4) { for_pairs_team<4>(n, f); return; }
-    if (coop == 16) { for_pairs_team<16>(n, f); return; }
+    if (coop == 4) { for_team<double, 4>(n, f); return; }
+    if (coop == 16) { for_team<double, 16>(n, f); return; }
 #pragma unroll kSimUnroll
     for (int i = 0; i < n; ++i) {
       double z0, z1;
@@ -877,120 +874,83 @@ struct NormalStream {
       f(z0, z1);
     }
   }
+  // ---- a team per particle
+  // the events of one group, lane J's after lane J - 1's, while f says go on and the bound allows
   template <int W, class F, int... J>
-  __device__ __forceinline__ void hand_out(const double g0, const double g1, F &f, lane_seq<J...>) {
-    (f(team_pick_ct<W, J>(g0), team_pick_ct<W, J>(g1)), ...);
+  __device__ __forceinline__ bool hand_out_events(const double ge, const double gu, const int max_events, int &count, F &f, lane_seq<J...>) {
+    bool go = true;
+    ((go = go && count < max_events && (++count, f(team_pick_ct<W, J>(ge), team_pick_ct<W, J>(gu)))), ...);
+    return go;
   }
-  template <int W, class F, int... J>
-  __device__ __forceinline__ void hand_out_first(const int m, const double g0, const double g1, F &f, lane_seq<J...>) {   // the first m < W pairs
-    ((J < m ? f(team_pick_ct<W, J>(g0), team_pick_ct<W, J>(g1)) : (void)0), ...);      // (m = W: all of them)
-  }
-  template <int W, int NB, class F>
-  __device__ __forceinline__ void tail(const int c, const int r, F &f) {      // (NB - 1) W < r <= NB W pairs from block k + c on
+  // blocks k + count + q on lane q, one block per lane per group
+  template <int W, class F>
+  __device__ __forceinline__ int while_events_team(const int max_events, F &f) {
     using lanes = typename make_lane_seq<W>::type;
     const uint32_t q = threadIdx.x & (uint32_t)(W - 1);
-    double g0[NB], g1[NB];
-#pragma unroll
-    for (int a = 0; a < NB; ++a) box_muller(stream_block(seed, pid, purpose, iter, k + (uint32_t)(c + W * a) + q), g0[a], g1[a]);
-#pragma unroll
-    for (int a = 0; a < NB - 1; ++a) hand_out<W>(g0[a], g1[a], f, lanes{});
-    hand_out_first<W>(r - (NB - 1) * W, g0[NB - 1], g1[NB - 1], f, lanes{});
+    int count = 0;
+    bool go = true;
+    while (go && count < max_events) {
+      const u32x4 w = stream_block(seed, pid, purpose, iter, k + (uint32_t)count + q);
+      const double ge = 0.5 * neg2_log_tab(u52(w.x, w.y)), gu = u52(w.z, w.w);
+      go = hand_out_events<W>(ge, gu, max_events, count, f, lanes{});
+    }
+    k += (uint32_t)count;
+    return count;
   }
-  template <int W, class F>
-  __device__ __forceinline__ void for_pairs_team(const int n, F &f) {
+  // for_pairs and for_quads_f32 (T = double | float): f with the normals of one block per lane, lane J's after lane J - 1's,
+  // for the first m <= W lanes (m = W, a constant where it is called: all of them, no comparison left).
+  // (The arity of f is spelled in place: through a helper per lane, one call deeper, the binary32 tail compiles differently.)
+  template <class T, int W, class F, int... J>
+  __device__ __forceinline__ void hand_out(const int m, const T (&g)[TeamDraws<T>::kPerBlock], F &f, lane_seq<J...>) {
+    using D = TeamDraws<T>;
+    if constexpr (D::kPerBlock == 2) ((J < m ? f(D::template pick_ct<W, J>(g[0]), D::template pick_ct<W, J>(g[1])) : (void)0), ...);
+    else ((J < m ? f(D::template pick_ct<W, J>(g[0]), D::template pick_ct<W, J>(g[1]), D::template pick_ct<W, J>(g[2]), D::template pick_ct<W, J>(g[3])) : (void)0), ...);
+  }
+  template <class T, int W, int NB, class F>
+  __device__ __forceinline__ void tail(const int c, const int r, F &f) {      // (NB - 1) W < r <= NB W blocks from block k + c on
+    using lanes = typename make_lane_seq<W>::type;
+    const uint32_t q = threadIdx.x & (uint32_t)(W - 1);
+    T g[NB][TeamDraws<T>::kPerBlock];
+#pragma unroll
+    for (int a = 0; a < NB; ++a) TeamDraws<T>::normals(stream_block(seed, pid, purpose, iter, k + (uint32_t)(c + W * a) + q), g[a]);
+#pragma unroll
+    for (int a = 0; a < NB - 1; ++a) hand_out<T, W>(W, g[a], f, lanes{});
+    hand_out<T, W>(r - (NB - 1) * W, g[NB - 1], f, lanes{});
+  }
+  template <class T, int W, class F>
+  __device__ __forceinline__ void for_team(const int n, F &f) {
     using lanes = typename make_lane_seq<W>::type;
     const uint32_t q = threadIdx.x & (uint32_t)(W - 1);
     int c = 0;
     for (; c + 4 * W <= n; c += 4 * W) {               // whole groups of 4 W: blocks k + c + W a + q, a = 0..3, on lane q
-      double g0[4], g1[4];
+      T g[4][TeamDraws<T>::kPerBlock];
 #pragma unroll
-      for (int a = 0; a < 4; ++a) box_muller(stream_block(seed, pid, purpose, iter, k + (uint32_t)(c + W * a) + q), g0[a], g1[a]);
-      hand_out<W>(g0[0], g1[0], f, lanes{});
-      hand_out<W>(g0[1], g1[1], f, lanes{});
-      hand_out<W>(g0[2], g1[2], f, lanes{});
-      hand_out<W>(g0[3], g1[3], f, lanes{});
-    }
-    const int r = n - c;                               // the rest, < 4 W pairs: ceil(r / W) blocks per lane, again side by side
-    if (r > 3 * W) tail<W, 4>(c, r, f);
-    else if (r > 2 * W) tail<W, 3>(c, r, f);
-    else if (r > W) tail<W, 2>(c, r, f);
-    else if (r > 0) tail<W, 1>(c, r, f);
+      for (int a = 0; a < 4; ++a) TeamDraws<T>::normals(stream_block(seed, pid, purpose, iter, k + (uint32_t)(c + W * a) + q), g[a]);
+#pragma unroll
+      for (int a = 0; a < 4; ++a) hand_out<T, W>(W, g[a], f, lanes{});
+    }                                                  // (not tail<T, W, 4>(c, 4 W, f): the team kernels compile differently)
+    const int r = n - c;                               // the rest, < 4 W blocks: ceil(r / W) blocks per lane, again side by side
+    if (r > 3 * W) tail<T, W, 4>(c, r, f);
+    else if (r > 2 * W) tail<T, W, 3>(c, r, f);
+    else if (r > W) tail<T, W, 2>(c, r, f);
+    else if (r > 0) tail<T, W, 1>(c, r, f);
     k += (uint32_t)n;
-  }
-  // ---- binary32 draws, a team per particle: for_pairs_team's scheme with four floats per block
-  template <int W, class F, int... J>
-  __device__ __forceinline__ void hand_out_f32(const float (&g)[4], F &f, lane_seq<J...>) {
-    (f(team_pick_ct_f32<W, J>(g[0]), team_pick_ct_f32<W, J>(g[1]), team_pick_ct_f32<W, J>(g[2]), team_pick_ct_f32<W, J>(g[3])), ...);
-  }
-  template <int W, class F, int... J>
-  __device__ __forceinline__ void hand_out_first_f32(const int m, const float (&g)[4], F &f, lane_seq<J...>) {   // the first m <= W blocks
-    ((J < m ? f(team_pick_ct_f32<W, J>(g[0]), team_pick_ct_f32<W, J>(g[1]), team_pick_ct_f32<W, J>(g[2]), team_pick_ct_f32<W, J>(g[3])) : (void)0), ...);
-  }
-  template <int W, int NB, class F>
-  __device__ __forceinline__ void tail_f32(const int c, const int r, F &f) {      // (NB - 1) W < r <= NB W blocks from block k + c on
-    using lanes = typename make_lane_seq<W>::type;
-    const uint32_t q = threadIdx.x & (uint32_t)(W - 1);
-    float g[NB][4];
-#pragma unroll
-    for (int a = 0; a < NB; ++a)
-      f32::box_muller_quad(stream_block(seed, pid, purpose, iter, k + (uint32_t)(c + W * a) + q), g[a][0], g[a][1], g[a][2], g[a][3]);
-#pragma unroll
-    for (int a = 0; a < NB - 1; ++a) hand_out_f32<W>(g[a], f, lanes{});
-    hand_out_first_f32<W>(r - (NB - 1) * W, g[NB - 1], f, lanes{});
-  }
-  template <int W, class F>
-  __device__ __forceinline__ void for_quads_team(const int n, F &f) {
-    using lanes = typename make_lane_seq<W>::type;
-    const uint32_t q = threadIdx.x & (uint32_t)(W - 1);
-    int c = 0;
-    for (; c + 4 * W <= n; c += 4 * W) {               // whole groups of 4 W: blocks k + c + W a + q, a = 0..3, on lane q
-      float g[4][4];
-#pragma unroll
-      for (int a = 0; a < 4; ++a)
-        f32::box_muller_quad(stream_block(seed, pid, purpose, iter, k + (uint32_t)(c + W * a) + q), g[a][0], g[a][1], g[a][2], g[a][3]);
-      hand_out_f32<W>(g[0], f, lanes{});
-      hand_out_f32<W>(g[1], f, lanes{});
-      hand_out_f32<W>(g[2], f, lanes{});
-      hand_out_f32<W>(g[3], f, lanes{});
-    }
-    const int r = n - c;                               // the rest, < 4 W blocks
-    if (r > 3 * W) tail_f32<W, 4>(c, r, f);
-    else if (r > 2 * W) tail_f32<W, 3>(c, r, f);
-    else if (r > W) tail_f32<W, 2>(c, r, f);
-    else if (r > 0) tail_f32<W, 1>(c, r, f);
-    k += (uint32_t)n;
-  }
-  // fetch for the binary32 draws: the group's blocks as four normals or four uniforms per lane
-  template <int W>
-  __device__ __forceinline__ void fetch_f32(uint32_t kk, bool uniform, float &x0, float &x1, float &x2, float &x3) {
-    const int base = (int)(kk & ~(uint32_t)(W - 1));
-    if (fbuf_block != base || fbuf_uniform != uniform) {
-      const u32x4 w = stream_block(seed, pid, purpose, iter, (uint32_t)base + (threadIdx.x & (uint32_t)(W - 1)));
-      if (uniform) f32::uniform_quad(w, fb0, fb1, fb2, fb3);
-      else f32::box_muller_quad(w, fb0, fb1, fb2, fb3);
-      fbuf_block = base;
-      fbuf_uniform = uniform;
-    }
-    x0 = team_pick_f32<W>(fb0, kk);
-    x1 = team_pick_f32<W>(fb1, kk);
-    x2 = team_pick_f32<W>(fb2, kk);
-    x3 = team_pick_f32<W>(fb3, kk);
   }
   // coop: block kk of the stream, from the lane of the team that holds it; a group of W blocks is (re)generated -- one block
   // per lane -- when the request leaves the buffered group or asks for the other kind (a simulator that mixes pair() and
   // uniform_pair() inside a group pays a refill for it, the stream it sees is still the stream)
-  template <int W>
-  __device__ __forceinline__ void fetch(uint32_t kk, bool uniform, double &x0, double &x1) {
+  template <int W, class T>
+  __device__ __forceinline__ void fetch(uint32_t kk, bool uniform, TeamBuf<T> &b, T (&x)[TeamDraws<T>::kPerBlock]) {
     const int base = (int)(kk & ~(uint32_t)(W - 1));
-    if (buf_block != base || buf_uniform != uniform) {
+    if (b.block != base || b.uniform != uniform) {
       const u32x4 w = stream_block(seed, pid, purpose, iter, (uint32_t)base + (threadIdx.x & (uint32_t)(W - 1)));
-      if (uniform) { b0 = u52(w.x, w.y); b1 = u52(w.z, w.w); }
-      else box_muller(w, b0, b1);
-      buf_block = base;
-      buf_uniform = uniform;
+      if (uniform) TeamDraws<T>::uniforms(w, b.v);
+      else TeamDraws<T>::normals(w, b.v);
+      b.block = base;
+      b.uniform = uniform;
     }
-    x0 = team_pick<W>(b0, kk);
-    x1 = team_pick<W>(b1, kk);
+#pragma unroll
+    for (int i = 0; i < TeamDraws<T>::kPerBlock; ++i) x[i] = team_pick<W>(b.v[i], kk);
   }
 };
 
@@ -1008,5 +968,5 @@ __device__ __forceinline__ void emit(NormalStream &rng, const long long i, const
 }  // namespace sabc
 
 #include "team_sample.hpp"     // sabc::Sample<N, W>: a sample spread over the lanes of a team (uses NormalStream, team_pick and emit above)
-#include "team_sample_f32.hpp" // sabc::SampleF32<N, W>: its binary32 twin, four normals per block (f32::box_muller_quad, team_pick_f32)
+#include "team_sample_f32.hpp" // sabc::SampleF32<N, W>: its binary32 twin, four normals per block (f32::box_muller_quad, team_pick)
 #include "team_series.hpp"     // sabc::Series<N, W>: a time series in time order over the team, lags through DPP (uses the above)

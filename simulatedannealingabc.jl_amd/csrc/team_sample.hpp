@@ -15,7 +15,7 @@
 //   costs today, the same bits.  So any N compiles for any W.
 //
 // Before the sort, draw i = normal i of the stream lies on the lane that generated its block b = i / 2 -- lane b mod W, the
-// assignment of NormalStream::for_pairs_team -- in slot 2 (b / W) + (i & 1).  After it, rank i lies on lane i / M in slot
+// assignment of NormalStream::for_team<double, W> -- in slot 2 (b / W) + (i & 1).  After it, rank i lies on lane i / M in slot
 // i mod M: position p = q M + r.  A sorting network is oblivious to where its inputs start, so no value moves between the two.
 //
 // The network is the bitonic one on P = W M positions: stages k = 2, 4, .., P, in each the steps j = k / 2, .., 1 that order
@@ -127,7 +127,7 @@ namespace teamsort {
 //   folded into a comparison of the lane with a constant, the two types transform and store in different orders, and behind one
 //   more call the same text is scheduled differently.)
 //   xor_lane<DIST>(v): v from lane ^ DIST of the row;  vmin, vmax, vmin_neg(a, b) = min(a, -b);  flip_sign(v, bit 31 or 0)
-//   select_slot(v, slot), pick<W>(v, lane): a slot and a lane known at run time
+//   select_slot(v, slot): a slot known at run time (the lane known at run time is device_rng.hpp's team_pick<W>, one text for both)
 //   the replicated store's fill_normals, order_statistic and quantile, as a simulator writes them by hand for this type
 template <class T>
 struct Element;
@@ -199,8 +199,6 @@ struct Element<double> {
     }
     return __hiloint2double(hi, lo);
   }
-  template <int W>
-  static __device__ __forceinline__ double pick(const double v, const uint32_t lane) { return team_pick<W>(v, lane); }
 
   template <int N, class F>
   static __device__ __forceinline__ void fill_normals(NormalStream &rng, double (&x)[N], F &&f) {
@@ -335,10 +333,10 @@ struct SampleStore : Element<T>::template Slots<N, W, slots(N, W, Element<T>::pe
     sorted = true;
   }
   __device__ __forceinline__ T drawn(const int i) const {
-    return E::template pick<W>(E::template select_slot<M>(v, draw_slot(i, W, P)), (uint32_t)draw_lane(i, W, P));
+    return team_pick<W>(E::template select_slot<M>(v, draw_slot(i, W, P)), (uint32_t)draw_lane(i, W, P));
   }
   __device__ __forceinline__ T at(const int i) const {
-    return E::template pick<W>(E::template select_slot<M>(v, rank_slot(i, M)), (uint32_t)rank_lane(i, M));
+    return team_pick<W>(E::template select_slot<M>(v, rank_slot(i, M)), (uint32_t)rank_lane(i, M));
   }
   __device__ __forceinline__ T order_statistic(const int rank) const {
     const T x = at(rank >= 1 && rank <= N ? rank - 1 : 0);             // (uniform over the team: every lane takes part)

@@ -4,7 +4,7 @@
 //
 //   Layout.  The normals come in blocks of FOUR (NormalStream::quad_f32) and a lane keeps all four normals of the blocks it
 //   generates: M = pow2ceil(4 ceil(ceil(N / 4) / W)) slots per lane, M <= kSortUnrollMax = 32, i.e. N <= 32 W as for doubles.  Draw
-//   i is normal i & 3 of block b = i >> 2 and lies on lane b mod W -- the assignment of NormalStream::for_quads_team / tail_f32 --
+//   i is normal i & 3 of block b = i >> 2 and lies on lane b mod W -- the assignment of NormalStream::for_team<float, W> / tail --
 //   in slot 4 (b / W) + (i & 3); after the sort rank i lies on lane i / M in slot i mod M.  Pad slots hold +inf.
 //   W = 1, or M > 32: the REPLICATED form, float x[N] filled through rng.for_quads_f32 and sorted by sabc::sort_ascending.
 //   Either way fill_normals consumes the ceil(N / 4) whole blocks rng.for_quads_f32(ceil(N / 4), ..) would, in that order.
@@ -21,7 +21,7 @@
 //   A DPP instruction written in asm is not an option: the compiler does not cover the write-then-DPP-read wait states of an asm
 //   text.  (DESIGN.md section 3 has the counts.)
 //
-//   Read-outs return float (drawn, at, order_statistic: a select over the slots, then team_pick_f32 -- no indexed access, the
+//   Read-outs return float (drawn, at, order_statistic: a select over the slots, then team_pick -- no indexed access, the
 //   slots stay registers); quantile(p) returns double, teamsort::quantile_at over the values widened to double (exact), the type-7
 //   arithmetic of the f64 form; emit writes (double)value.
 //
@@ -96,8 +96,6 @@ struct Element<float> {
     for (int r = 0; r < M; ++r) x = slot == r ? __float_as_int(v[r]) : x;
     return __int_as_float(x);
   }
-  template <int W>
-  static __device__ __forceinline__ float pick(const float v, const uint32_t lane) { return team_pick_f32<W>(v, lane); }
 
   template <int N, class F>
   static __device__ __forceinline__ void fill_normals(NormalStream &rng, float (&x)[N], F &&f) {
