@@ -341,7 +341,9 @@ class SabcHandle:
         return float(self._L.sabc_last_ess(self._h))
 
     def simulate(self, theta, pid0, it):
-        """theta [d][m] -> rho [s][m] with the RNG streams of particles pid0.. at iteration `it`."""
+        """theta [d][m] -> rho [s][m] with the RNG streams of particles pid0.. at iteration `it`.  The update that takes
+        counters["n_population_updates"] from k to k + 1 simulates local particle i as pid = local_offset + i at it = k + 1;
+        it runs a shard as the halves [0, h) and [h, n_local), h = n_local // 2, each with partners from the other half."""
         th = np.ascontiguousarray(theta, dtype=np.float64).reshape(self.d, -1)
         out = np.empty((self.s, th.shape[1]))
         self._check(self._L.sabc_op_simulate(self._h, _dp(th), th.shape[1], int(pid0), int(it), _dp(out)))
