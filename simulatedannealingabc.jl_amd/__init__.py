@@ -13,7 +13,7 @@ from .distributions import (Beta, Exponential, Gamma, HostPrior, LogNormal, MvNo
 from .handle import (SabcHandle, op_build_cdf, op_cdf_eval, op_eps_multi, op_eps_single,  # noqa: F401
                      op_normal_pairs, op_normal_quads_f32, op_philox, op_rng_peak, op_rng_peak_f32, op_sort)
 from .models import (DeviceDistance, DeviceSource, GandK, GandKQuantiles, GandKSample, GandKSampleF32, Gaussian2D, GaussianIID, HostDistance, LotkaVolterra, LotkaVolterraF32,  # noqa: F401
-                     GARCH11, MA2, NormalMoments, StochasticSIR, StochasticSIRSeries)
+                     GARCH11, MA2, NormalMoments, Ricker, StochasticSIR, StochasticSIRSeries)
 from .proposals import DifferentialEvolution, Proposal, RandomWalk, StretchMove  # noqa: F401
 
 __all__ = [
@@ -21,7 +21,7 @@ __all__ = [
     "RandomWalk", "DifferentialEvolution", "StretchMove", "Proposal",
     "Normal", "Uniform", "Exponential", "LogNormal", "Gamma", "Beta", "TruncatedNormal", "truncated", "MvNormal", "HostPrior", "SourcePrior", "from_scipy", "Product", "product_distribution",
     "DeviceDistance", "DeviceSource", "HostDistance", "GaussianIID", "Gaussian2D", "GandK", "LotkaVolterra", "StochasticSIR",
-    "NormalMoments", "StochasticSIRSeries", "LotkaVolterraF32", "GandKQuantiles", "GandKSample", "GandKSampleF32", "MA2", "GARCH11",
+    "NormalMoments", "StochasticSIRSeries", "LotkaVolterraF32", "GandKQuantiles", "GandKSample", "GandKSampleF32", "MA2", "GARCH11", "Ricker",
     "SabcHandle", "op_build_cdf", "op_cdf_eval", "op_eps_single", "op_eps_multi", "op_philox", "op_normal_pairs", "op_rng_peak", "op_sort",
     "op_normal_quads_f32", "op_rng_peak_f32",
     "build", "lib", "is_logging",

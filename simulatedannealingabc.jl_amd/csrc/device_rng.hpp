@@ -618,6 +618,128 @@ template <int... J> struct lane_seq {};
 template <int N, int... J> struct make_lane_seq : make_lane_seq<N - 1, N - 1, J...> {};
 template <int... J> struct make_lane_seq<0, J...> { using type = lane_seq<J...>; };
 
+// ---- count draws: the algorithms, written once over `next(u, v)`, the source of trial j's block -- the uniforms of the stream's
+// next block for NormalStream::poisson / binomial (below), those of block base + 64 i + j for CountDraws.  Every loop has a
+// compile-time bound (1000 inversion steps, kCountBlocks trials), so no draw can spin whatever its arguments are.
+// (Both take exp and log from this header -- exp_tab 1.79 ulp, log_fast 0.73 ulp, a few dozen instructions each.)
+constexpr int kCountBlocks = 64;             // the trial bound of PTRS and BTRS: the blocks a keyed draw owns
+constexpr int kMaxCountDraws = 1 << 20;      // the indices one reserve_counts may reserve
+constexpr double kMaxCount = 0x1p30;         // the largest lambda | n_trials
+
+namespace count {
+
+// Poisson(lambda), 0 < lambda <= 2^30.  lambda < 10: sequential-search inversion of u0 of ONE block (at most 1000 steps).
+// Otherwise Hoermann's PTRS (transformed rejection with squeeze, Insurance: Mathematics and Economics 12, 1993), one block per
+// trial, at most 64 trials (then floor(lambda); 1.15 - 1.33 trials per draw).
+template <class Next>
+__device__ __forceinline__ int poisson_from(const double lambda, Next &&next) {
+  double u, v;
+  if (lambda < 10.0) {
+    next(u, v);
+    double p = exp_tab(-lambda), c = p;
+    int k = 0;
+    while (u >= c && k < 1000) {
+      ++k;
+      p *= lambda / (double)k;
+      c += p;
+    }
+    return k;
+  }
+  const double b = 0.931 + 2.53 * sqrt(lambda), a = -0.059 + 0.02483 * b;
+  const double inv_alpha = 1.1239 + 1.1328 / (b - 3.4), vr = 0.9277 - 3.6224 / (b - 2.0);
+  const double log_lambda = log_fast(lambda), log_inv_alpha = log_fast(inv_alpha);
+  for (int trial = 0; trial < kCountBlocks; ++trial) {
+    next(u, v);
+    const double U = u - 0.5, us = 0.5 - fabs(U);
+    const double kf = floor((2.0 * a / us + b) * U + lambda + 0.43);
+    if (us >= 0.07 && v <= vr) return (int)kf;
+    if (kf < 0.0 || (us < 0.013 && v > us)) continue;
+    if (log_fast(v) + log_inv_alpha - log_fast(a / (us * us) + b) <= -lambda + kf * log_lambda - log_factorial(kf)) return (int)kf;
+  }
+  return (int)floor(lambda);
+}
+
+// Binomial(n, p), n >= 1, 0 < p <= 1/2.  n p < 10: sequential-search inversion of u0 of ONE block.  Otherwise Hoermann's BTRS
+// (J. Statist. Comput. Simul. 46, 1993), one block per trial, at most 64 trials (then the mode).
+template <class Next>
+__device__ __forceinline__ int binomial_lower_from(const int n, const double p, Next &&next) {
+  const double q = 1.0 - p, r = p / q, nd = (double)n;
+  double u, v;
+  if (nd * p < 10.0) {
+    next(u, v);
+    double pk = exp_tab(nd * log_fast(q)), c = pk;                   // (1 - p)^n, n p < 10
+    int k = 0;
+    while (u >= c && k < n && k < 1000) {                            // (n p < 10: P(k > 1000) = 0 in binary64; the bound is for a u above the rounded sum)
+      ++k;
+      pk *= r * (double)(n - k + 1) / (double)k;
+      c += pk;
+    }
+    return k;
+  }
+  const double spq = sqrt(nd * p * q), b = 1.15 + 2.53 * spq, a = -0.0873 + 0.0248 * b + 0.01 * p, c = nd * p + 0.5;
+  const double vr = 0.92 - 4.2 / b, alpha = (2.83 + 5.1 / b) * spq, m = floor((nd + 1.0) * p);
+  const double log_r = log_fast(r);
+  for (int trial = 0; trial < kCountBlocks; ++trial) {
+    next(u, v);
+    const double U = u - 0.5, us = 0.5 - fabs(U);
+    const double kf = floor((2.0 * a / us + b) * U + c);
+    if (us >= 0.07 && v <= vr) return (int)kf;
+    if (kf < 0.0 || kf > nd) continue;
+    // log f(k) / f(m) = log m! + log (n - m)! - log k! - log (n - k)! + (k - m) log r, summed in that order (most trials end at
+    // the squeeze above)
+    const double lf = log_factorial(m) + log_factorial(nd - m) - log_factorial(kf) - log_factorial(nd - kf);
+    if (log_fast(v * alpha / (a / (us * us) + b)) <= lf + (kf - m) * log_r) return (int)kf;
+  }
+  return (int)m;
+}
+
+}  // namespace count
+
+// Count draws KEYED BY AN INDEX (NormalStream::reserve_counts(n), below): draw index i owns the kCountBlocks = 64 blocks
+// base + 64 i .. base + 64 i + 63 of the stream's counter, trial j of a draw uses block base + 64 i + j (the inversion: trial 0),
+// and the uniforms of a block are those uniform_pair() returns for it.  The generator is counter-based, so a block nobody asks
+// for is never computed: the reserved range costs counter space alone.  A draw is therefore a PURE function of (i, its
+// parameters) -- cd.poisson(i, lambda) is what rng.poisson(lambda) returns from a lane-per-particle stream positioned at block
+// base + 64 i, the same algorithm constant for constant (count::poisson_from above) --, whichever lane computes it, in whatever
+// order, with whatever team width, and whether or not the result is kept.  The CALLING LANE computes the blocks with the plain
+// stream_block whatever the stream's coop is: no fetch, no DPP, no LDS beyond the elementary functions' tables.  So the lanes of
+// a team may draw for different indices side by side (Series::map, fill, zip: a lane draws for the slots it holds), and a draw
+// is legal inside Series::recur's f, which stays pure.
+// TOTAL: the relay of recur evaluates f on lanes that discard the result, so every argument has a value.  lambda NaN or <= 0: 0;
+// lambda > 2^30 is taken as 2^30.  n_trials (any arithmetic type, taken as a double) is clamped to [0, 2^30], a NaN to 0.  p NaN or <= 0: 0; p >= 1:
+// the clamped n_trials.  None of those degenerate cases computes a block.  Every loop keeps its bound: 1000 steps, 64 trials.
+// i is not checked: an index outside [0, n) reads blocks that belong to other draws of the stream.
+struct CountDraws {
+  uint64_t seed, pid, iter;
+  uint32_t purpose, base;
+
+  // trial j of index i: the uniforms of block base + 64 i + j
+  struct Trials {
+    const CountDraws &c;
+    uint32_t at;
+    __device__ __forceinline__ void operator()(double &u, double &v) {
+      const u32x4 w = stream_block(c.seed, c.pid, c.purpose, c.iter, at++);
+      u = u52(w.x, w.y);
+      v = u52(w.z, w.w);
+    }
+  };
+  __device__ __forceinline__ Trials trials(const int i) const { return Trials{*this, base + (uint32_t)kCountBlocks * (uint32_t)i}; }
+
+  __device__ __forceinline__ int poisson(const int i, const double lambda) const {
+    if (!(lambda > 0.0)) return 0;
+    return count::poisson_from(fmin(lambda, kMaxCount), trials(i));
+  }
+  // n_trials: any arithmetic type, taken as a double
+  template <class T>
+  __device__ __forceinline__ int binomial(const int i, const T n_trials, const double p) const {
+    const int n = (int)fmin(fmax((double)n_trials, 0.0), kMaxCount);   // (fmax(NaN, 0) = 0)
+    if (n <= 0 || !(p > 0.0)) return 0;
+    if (p >= 1.0) return n;
+    if (p > 0.5) return n - count::binomial_lower_from(n, 1.0 - p, trials(i));
+    return count::binomial_lower_from(n, p, trials(i));
+  }
+};
+
 // Sequential N(0,1) stream of one (particle, purpose, iteration): block k yields normals 2k, 2k+1.
 //
 // coop = 4 | 16 (k_update_persistent on small shards, persistent_kernel.hpp): the lanes of a TEAM -- a quad, or a row of 16 --
@@ -766,78 +888,40 @@ struct NormalStream {
     }
     return count;
   }
-  // (Both count draws take exp and log from this header -- exp_tab 1.79 ulp, log_fast 0.73 ulp, a few dozen instructions each.)
-  // Poisson(lambda), lambda <= 2^30.  lambda <= 0: 0, no block.  lambda < 10: sequential-search inversion of u0 of ONE block
-  // (at most 1000 steps).  Otherwise Hoermann's PTRS (transformed rejection with squeeze, Insurance: Mathematics and Economics
-  // 12, 1993), one block per trial, at most 64 trials (then floor(lambda); 1.15 - 1.33 trials per draw).
+  // Poisson(lambda), lambda <= 2^30.  lambda <= 0: 0, no block.  lambda < 10: inversion of u0 of ONE block; otherwise PTRS, one
+  // block per trial, at most 64 (count::poisson_from above, on the stream's next blocks).
   __device__ __forceinline__ int poisson(const double lambda) {
     if (!(lambda > 0.0)) return 0;
-    double u, v;
-    if (lambda < 10.0) {
-      uniform_pair(u, v);
-      double p = exp_tab(-lambda), c = p;
-      int k = 0;
-      while (u >= c && k < 1000) {
-        ++k;
-        p *= lambda / (double)k;
-        c += p;
-      }
-      return k;
-    }
-    const double b = 0.931 + 2.53 * sqrt(lambda), a = -0.059 + 0.02483 * b;
-    const double inv_alpha = 1.1239 + 1.1328 / (b - 3.4), vr = 0.9277 - 3.6224 / (b - 2.0);
-    const double log_lambda = log_fast(lambda), log_inv_alpha = log_fast(inv_alpha);
-    for (int trial = 0; trial < 64; ++trial) {
-      uniform_pair(u, v);
-      const double U = u - 0.5, us = 0.5 - fabs(U);
-      const double kf = floor((2.0 * a / us + b) * U + lambda + 0.43);
-      if (us >= 0.07 && v <= vr) return (int)kf;
-      if (kf < 0.0 || (us < 0.013 && v > us)) continue;
-      if (log_fast(v) + log_inv_alpha - log_fast(a / (us * us) + b) <= -lambda + kf * log_lambda - log_factorial(kf)) return (int)kf;
-    }
-    return (int)floor(lambda);
+    return count::poisson_from(lambda, [&](double &u, double &v) { uniform_pair(u, v); });
   }
-  // Binomial(n, p).  n <= 0 or p <= 0: 0, p >= 1: n, no block.  p > 1/2: n - binomial(n, 1 - p).  n p < 10: sequential-search
-  // inversion of u0 of ONE block.  Otherwise Hoermann's BTRS (J. Statist. Comput. Simul. 46, 1993), one block per trial, at
-  // most 64 trials (then the mode).
+  // Binomial(n, p).  n <= 0 or p <= 0: 0, p >= 1: n, no block.  p > 1/2: n - binomial(n, 1 - p).  n p < 10: inversion of u0 of
+  // ONE block; otherwise BTRS, one block per trial, at most 64 (count::binomial_lower_from above, on the stream's next blocks).
   __device__ __forceinline__ int binomial(const int n, const double p) {
     if (n <= 0 || !(p > 0.0)) return 0;
     if (p >= 1.0) return n;
-    if (p > 0.5) return n - binomial_lower(n, 1.0 - p);
-    return binomial_lower(n, p);
+    const auto next = [&](double &u, double &v) { uniform_pair(u, v); };
+    if (p > 0.5) return n - count::binomial_lower_from(n, 1.0 - p, next);
+    return count::binomial_lower_from(n, p, next);
+  }
+  // n draw indices 0 .. n - 1 for count draws keyed by an index (CountDraws above): records (seed, pid, purpose, iter, base = k)
+  // and advances k by kCountBlocks n = 64 n.  No block is generated.  0 <= n <= 2^20 = kMaxCountDraws: checked at compile time in
+  // the template form, clamped in the other.  THE COUNTER BUDGET: k has 32 bits, 2^32 blocks per (particle, purpose, iteration);
+  // a reservation of 2^20 indices takes 2^26 of them, and nothing checks the sum of a simulator's requests.
+  // The team buffers (buf64, buf32) and next()'s spare stay as they are: fetch compares the group of the block it is asked for
+  // with the group it holds and refills by itself when k has left it, and the spare is the second normal of a block consumed
+  // before the reservation, still the stream's next normal for next().
+  __device__ __forceinline__ CountDraws reserve_counts(const int n) {
+    const CountDraws cd{seed, pid, iter, purpose, k};
+    k += (uint32_t)kCountBlocks * (uint32_t)(n < 0 ? 0 : n > kMaxCountDraws ? kMaxCountDraws : n);
+    return cd;
+  }
+  template <int N>
+  __device__ __forceinline__ CountDraws reserve_counts() {
+    static_assert(N >= 0 && N <= kMaxCountDraws, "reserve_counts: 0 <= n <= 2^20 draw indices");
+    return reserve_counts(N);
   }
 
  private:
-  __device__ __forceinline__ int binomial_lower(const int n, const double p) {      // 0 < p <= 1/2
-    const double q = 1.0 - p, r = p / q, nd = (double)n;
-    double u, v;
-    if (nd * p < 10.0) {
-      uniform_pair(u, v);
-      double pk = exp_tab(nd * log_fast(q)), c = pk;                   // (1 - p)^n, n p < 10
-      int k = 0;
-      while (u >= c && k < n && k < 1000) {                            // (n p < 10: P(k > 1000) = 0 in binary64; the bound is for a u above the rounded sum)
-        ++k;
-        pk *= r * (double)(n - k + 1) / (double)k;
-        c += pk;
-      }
-      return k;
-    }
-    const double spq = sqrt(nd * p * q), b = 1.15 + 2.53 * spq, a = -0.0873 + 0.0248 * b + 0.01 * p, c = nd * p + 0.5;
-    const double vr = 0.92 - 4.2 / b, alpha = (2.83 + 5.1 / b) * spq, m = floor((nd + 1.0) * p);
-    const double log_r = log_fast(r);
-    for (int trial = 0; trial < 64; ++trial) {
-      uniform_pair(u, v);
-      const double U = u - 0.5, us = 0.5 - fabs(U);
-      const double kf = floor((2.0 * a / us + b) * U + c);
-      if (us >= 0.07 && v <= vr) return (int)kf;
-      if (kf < 0.0 || kf > nd) continue;
-      // log f(k) / f(m) = log m! + log (n - m)! - log k! - log (n - k)! + (k - m) log r, summed in that order (most trials end at
-      // the squeeze above)
-      const double lf = log_factorial(m) + log_factorial(nd - m) - log_factorial(kf) - log_factorial(nd - kf);
-      if (log_fast(v * alpha / (a / (us * us) + b)) <= lf + (kf - m) * log_r) return (int)kf;
-    }
-    return (int)m;
-  }
   // a lane per particle: the loop over the stream's blocks in its re-spelled form (namespace loop; same bits as event_pair)
   template <class F>
   __device__ __forceinline__ int while_events_lane(const int max_events, F &f) {

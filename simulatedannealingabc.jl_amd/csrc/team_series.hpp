@@ -39,6 +39,18 @@
 //   recurrence is not divided; the draws, maps, zips, summaries and registers around it are.  series::run_recur is the schedule
 //   on plain arrays.
 //
+//   Count draws (state-space models with count observations: Ricker, branching processes, chain-binomial epidemics in time
+//   order).  NormalStream::poisson / binomial consume a data-dependent number of blocks of the ONE sequential counter, so a draw
+//   at time t cannot start before the draw at t - 1 has ended, and inside map / fill / zip -- a lane runs its own slots only --
+//   the lanes of a team would make different requests of the shared generator.  A series draws its counts KEYED BY THE TIME STEP
+//   instead (CountDraws, device_rng.hpp): cd = rng.reserve_counts(N) gives draw index t the 64 blocks base + 64 t .. + 63, and
+//   cd.poisson(t, lambda) / cd.binomial(t, n, p) are pure functions of their arguments that the calling lane computes alone.
+//   In map / fill / zip a lane draws for the slots it holds: the draws of a series are DIVIDED among the team (the replicated
+//   store: every lane all N).  map_poisson(rng, scale) is x_t <- Poisson(scale x_t) with index t, the slot loop rolled.
+//   Inside recur / recur_with f may call the const members of a CountDraws -- they are pure, the relay's discarded evaluations
+//   are harmless -- and still may not draw from rng.  The recurrence is NOT divided: every lane issues all N draws, a row of 16
+//   lanes sixteen times the draws of one lane.
+//
 // Out of scope: a parallel scan for associative operations (its rounding would depend on the order of association, other bits
 // than the loop's); a binary32 twin; lags between two series other than through lag<L>() followed by zip.
 //
@@ -243,6 +255,21 @@ struct SeriesStore {
     for (int r = 0; r < M; ++r)
       if (time_of(q, r, M) < N) v[r] = g(time_of(q, r, M), v[r], other.v[r]);
   }
+  // map with the slot loop ROLLED, for a g whose text is long (a count draw is a few hundred instructions, and map's unrolled
+  // loop would hold up to 32 copies of it): ONE copy of g; the slot of the trip is read and written through selects against the
+  // trip's number (select_slot and its mirror image, 4 M v_cndmask_b32 per trip), so the values stay in registers.
+  template <class G>
+  __device__ __forceinline__ void map_rolled(G &&g) {
+    const int q = lane();
+#pragma unroll 1
+    for (int r = 0; r < M; ++r) {
+      const int t = time_of(q, r, M);
+      const double x = teamsort::Element<double>::select_slot<M>(v, r);
+      const double y = t < N ? g(t, x) : x;
+#pragma unroll
+      for (int j = 0; j < M; ++j) v[j] = j == r ? y : v[j];
+    }
+  }
   __device__ __forceinline__ double at(const int t) const {
     return team_pick<W>(teamsort::Element<double>::select_slot<M>(v, time_slot(t, M)), (uint32_t)time_lane(t, M));
   }
@@ -356,6 +383,41 @@ struct SeriesStore {
   __device__ __forceinline__ State recur_two(const SeriesStore &other, State s, F &&f, const int first) {
     return recur_store(s, [&](const int t, State &c, const int r) { return f(t, c, v[r], other.v[r]); }, first);
   }
+  // The same relay with the loops over phases and slots ROLLED, for an f whose text is long (one that draws counts: the
+  // unrolled relay holds relay_lanes M copies of f, 128 count draws at N = 128): ONE copy of f.  The slot of the trip is read
+  // and written through selects against the trip's number, as in map_rolled, and the phase's lane is picked at run time
+  // (team_pick<W>, a branch per bit of the phase, uniform over the team).  f at slot r reads slot r alone, so writing the kept
+  // output at once is what recur_phase does behind its loop.  The same applications of f to the same arguments: the same bits.
+  template <class State, class F>
+  __device__ __forceinline__ State recur_store_rolled(State s, F &&f, const int first) {
+    const int q = lane();
+#pragma unroll 1
+    for (int p = 0; p < relay_lanes(N, M); ++p) {
+      State mine = s;
+#pragma unroll 1
+      for (int r = 0; r < M; ++r) {
+        const int t = time_of(q, r, M);
+        const bool live = first <= t && t < N;
+        const double x = teamsort::Element<double>::select_slot<M>(v, r);
+        State next = mine;
+        const double o = f(t, next, r, x);
+#pragma unroll
+        for (int k = 0; k < CarryOf<State>::size; ++k)
+          CarryOf<State>::at(mine, k) = live ? CarryOf<State>::at(next, k) : CarryOf<State>::at(mine, k);
+        const double keep = live && q == p ? o : x;
+#pragma unroll
+        for (int j = 0; j < M; ++j) v[j] = j == r ? keep : v[j];
+      }
+      // by every lane of the team, in uniform control flow
+#pragma unroll
+      for (int k = 0; k < CarryOf<State>::size; ++k) CarryOf<State>::at(s, k) = team_pick<W>(CarryOf<State>::at(mine, k), (uint32_t)p);
+    }
+    return s;
+  }
+  template <class State, class F>
+  __device__ __forceinline__ State recur_one_rolled(State s, F &&f, const int first) {
+    return recur_store_rolled(s, [&](const int t, State &c, const int, const double x) { return f(t, c, x); }, first);
+  }
 };
 
 // ---- replicated: a lane per particle, or a series too long for the team's registers ----
@@ -390,6 +452,11 @@ struct SeriesStore<N, W, false> {
   __device__ __forceinline__ void zip(const SeriesStore &other, G &&g) {
     for (int t = 0; t < N; ++t) x[t] = g(t, x[t], other.x[t]);
   }
+  template <class G>
+  __device__ __forceinline__ void map_rolled(G &&g) {
+#pragma unroll 1
+    for (int t = 0; t < N; ++t) x[t] = g(t, x[t]);
+  }
   __device__ __forceinline__ double at(const int t) const { return x[t]; }
   __device__ __forceinline__ void emit(NormalStream &rng, const long long first_output, const int first) const {
     if (!emitting(rng) || (threadIdx.x & (unsigned)(W - 1)) != 0) return;
@@ -416,6 +483,9 @@ struct SeriesStore<N, W, false> {
     for (int t = first > 0 ? first : 0; t < N; ++t) x[t] = f(t, s, x[t], other.x[t]);
     return s;
   }
+  // (the plain loop is rolled as it stands)
+  template <class State, class F>
+  __device__ __forceinline__ State recur_one_rolled(State s, F &&f, const int first) { return recur_one(s, f, first); }
 };
 
 }  // namespace series
@@ -437,7 +507,14 @@ struct SeriesStore<N, W, false> {
 //   Elements t < first are left as they are and do not touch the state.  The bits are the sequential loop's for every W.
 //   THE CONTRACT ON f: a pure function of its arguments.  The library may evaluate it on lanes that discard the result (the relay
 //   at the head of this file), so f has no side effects: it does not call emit, does not draw from rng and does not use the
-//   state as an index into memory.
+//   state as an index into memory.  f MAY call the const members of a sabc::CountDraws (cd.poisson(t, lambda),
+//   cd.binomial(t, n, p) with cd = rng.reserve_counts(N) taken in front of the recurrence): they are pure and total.  THE COST:
+//   the recurrence is not divided, so every lane of the team issues all N draws -- a row of 16 lanes 16 times the draws of one.
+//   recur_rolled(s0, f, first = 0): recur with the relay's loops rolled, ONE copy of f in the text where recur holds
+//   one per time step (a count draw is a few hundred instructions); the same bits.  The form for an f that draws.
+//   map_poisson(rng, scale = 1.0): x_t <- Poisson(scale x_t), the draw keyed by t (reserves N indices itself); a lane draws for
+//   its own slots (spread) or for all N (replicated).  The plain spelling through map gives the same values:
+//   cd = rng.reserve_counts(N); x.map([&](int t, double v) { return (double)cd.poisson(t, rounded_product(scale, v)); }).
 //   ROUNDING IS THE CALLER'S: the run-time compiler is told -ffp-contract=fast, so an a * b + c inside f may fuse on the device
 //   and not in a transcription.  f writes fma(...) where it wants one and series::rounded_product where it wants a product
 //   rounded on its own.  cumsum only adds.
@@ -486,8 +563,23 @@ struct Series : series::SeriesStore<N, W, teamsort::spread(N, W)>, teamsort::Sum
     static_assert(series::CarryOf<State>::size >= 1, "double or Carry<K>");
     return Store::recur_two(other, s0, f, first);
   }
+  // recur for an f whose text is long -- one that draws counts --: one copy of f in the text where recur holds one
+  // per time step a lane walks (N of them), the same bits
+  template <class State, class F>
+  __device__ __forceinline__ State recur_rolled(const State s0, F &&f, const int first = 0) {
+    static_assert(series::CarryOf<State>::size >= 1, "double or Carry<K>");
+    return Store::recur_one_rolled(s0, f, first);
+  }
   __device__ __forceinline__ void cumsum() {
     recur(0.0, [](const int, double &s, const double x) { s = s + x; return s; });
+  }
+  // x_t <- Poisson(scale x_t) for every t < N, the draw keyed by t: reserves N draw indices (64 N blocks of counter space, none
+  // generated unless a trial asks for it) and draws with index t, the product scale x_t rounded on its own.  The same values as
+  //   cd = rng.reserve_counts(N); x.map([&](int t, double v) { return (double)cd.poisson(t, rounded_product(scale, v)); })
+  // with one copy of the draw in the text where map would hold one per slot.
+  __device__ __forceinline__ void map_poisson(NormalStream &rng, const double scale = 1.0) {
+    const CountDraws cd = rng.template reserve_counts<N>();
+    Store::map_rolled([&](const int t, const double v) { return (double)cd.poisson(t, series::rounded_product(scale, v)); });
   }
 };
 

@@ -20,7 +20,7 @@ import Dates
 import Base: show
 
 export sabc, update_population!, RandomWalk, DifferentialEvolution, StretchMove,
-       DeviceDistance, GaussianIID, Gaussian2D, GandK, LotkaVolterra, DeviceSource, StochasticSIR, LotkaVolterraF32, NormalMoments, StochasticSIRSeries, GandKQuantiles, GandKSample, GandKSampleF32, MA2, GARCH11, SourcePrior,
+       DeviceDistance, GaussianIID, Gaussian2D, GandK, LotkaVolterra, DeviceSource, StochasticSIR, LotkaVolterraF32, NormalMoments, StochasticSIRSeries, GandKQuantiles, GandKSample, GandKSampleF32, MA2, GARCH11, Ricker, SourcePrior,
        comm_unique_id, simulate_outputs, posterior_predictive
 
 const libsabc = get(ENV, "SABC_HIP_LIB", joinpath(@__DIR__, "..", "libsabc_hip.so"))
@@ -423,6 +423,47 @@ function garch11_summaries(y, n_lags)
     c = tree_sum(r) / length(r)
     d = r .- c
     vcat(c, Float64[tree_sum(vcat(zeros(j), d[(j + 1):end] .* d[1:(end - j)])) / length(r) for j in 0:n_lags])
+end
+"""
+    Ricker(; summaries_obs=nothing, n_obs=50, burn_in=50, n_lags=5, n0=1.0, team_lanes=nothing)
+    Ricker(y_obs; burn_in=50, n_lags=5, n0=1.0, team_lanes=nothing)
+
+The Ricker map with Poisson observations (Wood 2010): θ = (log r, σ, φ), N_{t+1} = r N_t exp(−N_t + σ z_t) from N_0 = `n0` for
+`burn_in + n_obs` times, y_t ~ Poisson(φ N_{t+1}), the last `n_obs` counts observed.  Summaries: the mean, the number of zeros and
+the autocovariances about the mean at lags 0 .. `n_lags` (at most 7): ρ_0 = |mean(y) − obs[0]|, ρ_1 = |#{y_t = 0} − obs[1]|,
+ρ_{2+j} = |acov_j(y) − obs[2+j]|.  One data segment, `summaries_obs`, of `n_lags + 3` finite values; the second method takes it
+from an observed series of counts (`ricker_summaries`: the device's own sums).  A `DeviceSource` of device_sources/ricker.hip on
+`sabc::Series` (csrc/team_series.hpp): one recurrence in time order, then `map_poisson` -- count draws keyed by the time step
+(`sabc::CountDraws`), which a team divides among its lanes.  `team_lanes` = 1, 4 or 16: that many lanes per particle, the same
+bits as the default (`nothing`: a private array per lane).
+"""
+function Ricker(; summaries_obs=nothing, n_obs::Integer=50, burn_in::Integer=50, n_lags::Integer=5, n0::Real=1.0, team_lanes=nothing)
+    0 <= n_lags <= 7 || throw(ArgumentError("n_lags must be in 0..7"))
+    n_lags < n_obs || throw(ArgumentError("n_obs must be above n_lags"))
+    (burn_in >= 0 && burn_in + n_obs <= 1024) || throw(ArgumentError("burn_in must be non-negative and burn_in + n_obs at most 1024"))
+    (isfinite(n0) && n0 > 0) || throw(ArgumentError("n0 must be a positive finite number"))
+    text = read(joinpath(@__DIR__, "..", "device_sources", "ricker.hip"), String)
+    head = "#define RICKER_N_OBS $(n_obs)\n#define RICKER_BURN_IN $(burn_in)\n#define RICKER_N_LAGS $(n_lags)\n" *
+           (team_lanes === nothing ? "" : "#define RICKER_TEAM 1\n")
+    DeviceSource(head * text, 3, Int(n_lags) + 3; params=Float64[n_obs, burn_in, n_lags, n0],
+                 data=summaries_obs === nothing ? nothing : (summaries_obs,), data_names=(:summaries_obs,),
+                 validate=segs -> check_ricker_data(segs, Int(n_lags)), team_lanes=team_lanes)
+end
+function Ricker(y_obs; burn_in::Integer=50, n_lags::Integer=5, n0::Real=1.0, team_lanes=nothing)
+    obs = ricker_summaries(data_segment(y_obs), n_lags, burn_in)
+    Ricker(; summaries_obs=obs, n_obs=length(y_obs), burn_in=burn_in, n_lags=n_lags, n0=n0, team_lanes=team_lanes)
+end
+# the source reads summaries_obs[j] and writes ρ[j] for every j < n_lags + 3
+check_ricker_data(segs, n_lags) = (length(segs) == 1 && length(segs[1]) == n_lags + 3 && all(isfinite, segs[1])) ||
+    throw(ArgumentError("summaries_obs is one segment of $(n_lags + 3) finite values"))
+# mean(y), #{y_t = 0}, acov_0(y) .. acov_n_lags(y) as the device computes them: the tree over the burn_in + n times, the burn-in's
+# terms +0.0, rounded products, divided by n
+function ricker_summaries(y, n_lags, burn_in)
+    lead = zeros(burn_in)
+    c = tree_sum(vcat(lead, y)) / length(y)
+    d = y .- c
+    vcat(c, tree_sum(vcat(lead, Float64.(y .== 0))),
+         Float64[tree_sum(vcat(lead, zeros(j), d[(j + 1):end] .* d[1:(end - j)])) / length(y) for j in 0:n_lags])
 end
 """
     SourcePrior(d)

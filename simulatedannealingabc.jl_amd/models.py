@@ -256,6 +256,13 @@ class DeviceSource(DeviceDistance):
     the bits are the plain loop's for every width.  f must be a pure function of its arguments -- no emit, no draw from rng, no
     memory indexed by the state: the team evaluates it on lanes that discard the result -- and the rounding inside f is the
     caller's (write `fma` and `sabc::series::rounded_product`; a bare a * b + c may fuse).  `GARCH11` is the shipped model on it.
+    Counts keyed by the time step: `sabc::CountDraws cd = rng.reserve_counts(n)` (csrc/device_rng.hpp) reserves 64 blocks of the
+    stream's counter for each draw index 0 .. n-1 (n <= 2^20; no block is generated) and `cd.poisson(i, lambda)`,
+    `cd.binomial(i, n_trials, p)` are PURE functions of their arguments -- `rng.poisson` / `rng.binomial` from a stream positioned
+    at the index's first block, computed by the calling lane alone --, so the lanes of a team may draw for different indices side
+    by side (inside `map`, `fill`, `zip`) and a draw is legal inside `recur`'s f (every lane then issues all N draws).  They are
+    total: lambda NaN or <= 0 gives 0, lambda and n_trials above 2^30 count as 2^30, p NaN or <= 0 gives 0, p >= 1 n_trials.
+    `x.map_poisson(rng, scale = 1.0)` is x_t <- Poisson(scale x_t) with index t.  `Ricker` is the shipped model on these.
     Not there: a parallel scan for associative operations, a binary32 twin."""
     model_id = _lib.MODEL_USER
 
@@ -758,5 +765,84 @@ class GARCH11(DeviceSource):
         if len(segments) != 1 or len(segments[0]) != self.n_lags + 2:
             raise ValueError(f"summaries_obs is one segment of n_lags + 2 = {self.n_lags + 2} values (the mean of the squared returns and "
                              f"their autocovariances at lags 0 .. {self.n_lags})")
+        if not np.all(np.isfinite(segments[0])):
+            raise ValueError("summaries_obs must be finite")
+
+
+class Ricker(DeviceSource):
+    """The Ricker map with Poisson observations (Wood 2010), the model shipped on count draws keyed by the time step
+    (`sabc::CountDraws`, `sabc::Series::map_poisson`): theta = (log r, sigma, phi), N_{t+1} = r N_t exp(-N_t + sigma z_t) for
+    t = 0 .. burn_in + n_obs - 1 from N_0 = `n0`, with z the next normals of the particle's stream, and y_t ~ Poisson(phi N_{t+1});
+    the last n_obs counts are the observation.  Summaries of them: the mean, the number of zeros, and the autocovariances about
+    the mean at lags 0 .. n_lags (n_lags <= 7): rho_0 = |mean(y) - obs_0|, rho_1 = |#{t: y_t = 0} - obs_1|, rho_{2+j} =
+    |acov_j(y) - obs_{2+j}|: n_stats = n_lags + 3.  `summaries_obs` is ONE data segment of n_lags + 3 finite values -- another
+    series' summaries are another `SabcHandle.set_data` or `sabc(model, prior, summaries_obs=...)`, never another compilation --;
+    `n_obs`, `burn_in` and `n_lags` are compile-time constants of the source, `n0` is one of its params.
+    `from_observations(y_obs)` computes `summaries_obs` from a series of counts with the device's own sums (`summaries`),
+    `observe(theta)` lets the device source simulate one.
+    Source: device_sources/ricker.hip on `sabc::Series<burn_in + n_obs, W>` (csrc/team_series.hpp): the noise sigma z_t, one
+    `recur` with the state N_t (exp_tab and a product rounded on its own), `map_poisson(rng, phi)` -- the draw of time t owns 64
+    blocks of the counter, so a lane of a team draws for the times it holds --, then the canonical sums over t >= burn_in.
+    `team_lanes` = 1, 4 or 16: the series spread over that many lanes per particle; None (the default): the same text with a
+    private array per lane.  All forms give the same bits.  Outputs: the counts y_t, t >= burn_in (`posterior_predictive` gives
+    [n, n_rep, n_obs])."""
+    MAX_LAGS = 7
+    MAX_TIMES = 1024                 # burn_in + n_obs: the series is 8 bytes per time of private memory per lane where it is not spread (twice)
+
+    def __init__(self, summaries_obs=None, n_obs=50, burn_in=50, n_lags=5, n0=1.0, team_lanes=None, data_names=("summaries_obs",)):
+        if isinstance(n_lags, (bool, str)) or int(n_lags) != n_lags or not 0 <= int(n_lags) <= self.MAX_LAGS:
+            raise ValueError(f"n_lags must be an integer in 0..{self.MAX_LAGS}, got {n_lags!r}")
+        if isinstance(n_obs, (bool, str)) or int(n_obs) != n_obs or not int(n_lags) < int(n_obs) <= self.MAX_TIMES:
+            raise ValueError(f"n_obs must be an integer above n_lags = {n_lags} and at most {self.MAX_TIMES}, got {n_obs!r}")
+        if isinstance(burn_in, (bool, str)) or int(burn_in) != burn_in or not 0 <= int(burn_in) <= self.MAX_TIMES - int(n_obs):
+            raise ValueError(f"burn_in must be a non-negative integer with burn_in + n_obs <= {self.MAX_TIMES}, got {burn_in!r}")
+        if isinstance(n0, (bool, str)) or not (np.isfinite(float(n0)) and float(n0) > 0.0):
+            raise ValueError(f"n0 must be a positive finite number, got {n0!r}")
+        self.n_obs, self.burn_in, self.n_lags, self.n0 = int(n_obs), int(burn_in), int(n_lags), float(n0)
+        head = (f"#define RICKER_N_OBS {self.n_obs}\n#define RICKER_BURN_IN {self.burn_in}\n#define RICKER_N_LAGS {self.n_lags}\n"
+                + ("" if team_lanes is None else "#define RICKER_TEAM 1\n"))
+        super().__init__(head + device_source_text("ricker"), 3, self.n_lags + 3, [self.n_obs, self.burn_in, self.n_lags, self.n0],
+                         data=None if summaries_obs is None else [_segment(summaries_obs)], data_names=data_names,
+                         n_outputs=self.n_obs, team_lanes=team_lanes)
+
+    @staticmethod
+    def summaries(y, n_lags=5, burn_in=0):
+        """mean(y), #{t: y_t = 0}, acov_0(y) .. acov_n_lags(y) of a series of observed counts y (along the last axis) as the
+        device computes them: the canonical sum over the burn_in + n_obs times of the simulated series, the burn-in's terms +0.0
+        (the tree's shape, and with it the rounding of the autocovariances, depends on them; the sums of counts are exact
+        integers in any shape), every product rounded on its own, the autocovariances about the mean and divided by n_obs."""
+        y = np.asarray(y, dtype=np.float64)
+        n, lead = y.shape[-1], np.zeros(y.shape[:-1] + (int(burn_in),))
+        mean = _tree_sum(np.concatenate([lead, y], axis=-1)) / float(n)
+        zeros = _tree_sum(np.concatenate([lead, (y == 0.0).astype(np.float64)], axis=-1))
+        d = y - mean[..., None]
+        out = [mean, zeros]
+        for j in range(int(n_lags) + 1):
+            terms = np.zeros(y.shape)
+            terms[..., j:] = d[..., j:] * d[..., :n - j]
+            out.append(_tree_sum(np.concatenate([lead, terms], axis=-1)) / float(n))
+        return np.stack(out, axis=-1)
+
+    @classmethod
+    def from_observations(cls, y_obs, burn_in=50, n_lags=5, n0=1.0, team_lanes=None):
+        """The model for an observed series of counts `y_obs`: n_obs = len(y_obs), summaries_obs = `summaries(y_obs, n_lags, burn_in)`."""
+        y_obs = _segment(y_obs)
+        if isinstance(burn_in, (bool, str)) or int(burn_in) != burn_in or int(burn_in) < 0:
+            raise ValueError(f"burn_in must be a non-negative integer, got {burn_in!r}")
+        return cls(cls.summaries(y_obs, n_lags, burn_in), n_obs=len(y_obs), burn_in=burn_in, n_lags=n_lags, n0=n0, team_lanes=team_lanes)
+
+    @classmethod
+    def observe(cls, theta, n_obs=50, burn_in=50, seed=None, n0=1.0, device=None):
+        """A series of n_obs counts made by the device source itself: one forward run at theta = (log r, sigma, phi) on the
+        predictive stream of particle 0, iteration 0 of `seed`."""
+        from .api import simulate_outputs
+        model = cls(np.zeros(3), n_obs=n_obs, burn_in=burn_in, n_lags=0, n0=n0)
+        return simulate_outputs(model, np.asarray(theta, dtype=np.float64).reshape(1, 3), seed=seed, device=device)[0, 0]
+
+    def validate_data(self, segments):
+        # the source reads summaries_obs[j] and writes rho[j] for every j < n_lags + 3
+        if len(segments) != 1 or len(segments[0]) != self.n_lags + 3:
+            raise ValueError(f"summaries_obs is one segment of n_lags + 3 = {self.n_lags + 3} values (the mean of the counts, the number of "
+                             f"zeros and the autocovariances at lags 0 .. {self.n_lags})")
         if not np.all(np.isfinite(segments[0])):
             raise ValueError("summaries_obs must be finite")
